@@ -88,6 +88,9 @@ def parse():
                          "socket instead of failing (testing only; the line then says exchange=ctl-host-gather)")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary timed regions of the default run (single-query 10M x 768 f16; 256 int8 queries per pass; one query over 690k x 768 int8)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, <= 64 MB in "
+                         "all): the same arguments give the same inputs, so two builds can be compared output for output")
     ap.add_argument("--debug", action="append", default=[], metavar="KEY=VALUE",
                     help="pvs_debug_set(KEY, VALUE) before the run (tuning sweeps: sample_div, sample_j_div, scan_no_wide128, ...; the line records it)")
     a = ap.parse_args()
@@ -116,6 +119,27 @@ def replay_traffic(rows, dim, dtype, batch):
             return tj.get("hbm_bytes_per_launch"), (f"replayed from profiles/ (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this region's command, "
                                                     f"{tj.get('collected', 'date not recorded')}, kernel {str(tj.get('kernel', ''))[:48]}); not measured in this run")
     return None, None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, lead, log):
+    """--dump-outputs: one .npy per array of `arrays` (name -> array whose first axis has `lead` entries, one per query).  Floats keep
+    their width, integers become float64 (exact below 2^53).  Over DUMP_LIMIT_BYTES a fixed, seeded sample of the queries is kept,
+    the same one in every array, and its indices are written as query_index.npy."""
+    arrays = {n: np.asarray(a) for n, a in arrays.items()}
+    arrays = {n: a if a.dtype in (np.float32, np.float64) else a.astype(np.float64) for n, a in arrays.items()}
+    per_query = sum(a.nbytes for a in arrays.values()) // max(lead, 1) + 8
+    keep = min(lead, DUMP_LIMIT_BYTES // max(per_query, 1))
+    if keep < lead:
+        sel = np.sort(np.random.default_rng(0).choice(lead, keep, replace=False))
+        arrays = {n: a[sel] for n, a in arrays.items()}
+        arrays["query_index"] = sel.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for n, a in arrays.items():
+        np.save(os.path.join(dirname, n + ".npy"), np.ascontiguousarray(a))
+    log(f"outputs of the last timed step -> {dirname}: " + ", ".join(f"{n} {a.dtype}{list(a.shape)}" for n, a in arrays.items()))
 
 
 def summarize_secondary(secondary):
@@ -277,6 +301,9 @@ def run_config4(args, ctl, rank, world, device, real_stdout):
     elapsed = ctl.max_float(time.perf_counter() - t0)
     for b in branches:
         b["index"].set_profiling(False)
+    if args.dump_outputs and rank == 0:  # the composed query's page: file ids and fused scores
+        dump_outputs(args.dump_outputs, {"group_ids": last[0][None], "scores": last[1][None]}, 1,
+                     lambda m: print("[bench] " + m, file=sys.stderr, flush=True))
     # Kernel durations: in the timed region the two branches are scored from two host threads and their kernels overlap — each one's
     # event bracket then includes the share of HBM the other takes.  Exclusive durations come from a serialized second pass over the
     # same queries (pvs_debug_set("rrf_serial", 1)), like the several-streams case of the row search.
@@ -449,6 +476,8 @@ def launch_ranks(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: start the N ranks (one process per GPU) ourselves, relay rank 0's
     JSON line, fail if any rank fails."""
     sock = os.path.join(tempfile.gettempdir(), f"pvs_ctl_{os.getpid()}.sock")
+    if len(sock) > 100:  # an AF_UNIX path holds at most 107 bytes
+        sock = f"/tmp/pvs_ctl_{os.getpid()}.sock"
     procs = []
     for r in range(n):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), PVS_CTL_SOCK=sock, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -672,11 +701,16 @@ def main():
     ix.profile(reset=True)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        step(args.warmup + i)
+        last = step(args.warmup + i)
     drain()
     device_sync()
     ctl.barrier()
     elapsed = ctl.max_float(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:  # the page of every query of the last timed batch: row ids, distances, hits per query
+        if last is None:  # the page sits in the output slot of the last step
+            oi, od, oc = outs[(args.warmup + args.steps - 1) % slots]
+            last = oi.to_numpy(np.int64, (B, K)), od.to_numpy(np.float32, (B, K)), oc.to_numpy(np.uint32, (B,))
+        dump_outputs(args.dump_outputs, {"ids": last[0], "distances": last[1], "counts": last[2]}, B, log)
     ix.set_profiling(False)
     prof = ix.profile()
     if overlapped and not args.no_kernel_events:

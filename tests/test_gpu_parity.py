@@ -185,8 +185,6 @@ CASES = [
 @pytest.mark.parametrize("dtype,metric,n,dim,batch,k", CASES)
 @pytest.mark.parametrize("path", ["auto", "dense"])
 def test_search_matches_oracle(pvs, dtype, metric, n, dim, batch, k, path):
-    if path == "dense" and (n > 12000 or batch > 8):
-        pytest.skip("dense path covered on the smaller cases")
     dt = {"i8": pvs.I8, "f16": pvs.F16, "f32": pvs.F32}[dtype]
     m = pvs.COSINE if metric == "cosine" else pvs.L2
     rows = unit_rows(3, n, dim)

@@ -385,3 +385,36 @@ def test_exact_wide_instances_use_no_scratch(tmp_path):
     found = re.findall(r"\.name:\s+(\S*k_exact_wide\S*)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)", out.read_text())
     assert len(found) == 8, found
     assert all(int(p) == 0 for _, p in found), found
+
+
+def test_bench_dump_outputs_writes_floats_within_the_limit(tmp_path):
+    """bench.py --dump-outputs: integer pages come back as exact float64, and a page over the size limit is cut to a seeded
+    sample of whole queries, the same sample on every call."""
+    import importlib.util
+
+    spec = importlib.util.spec_from_file_location("bench_for_dump", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    ids = rng.integers(0, 2**40, (64, 10), dtype=np.int64)
+    dist = rng.standard_normal((64, 10)).astype(np.float32)
+    cnt = np.full(64, 10, np.uint32)
+    small = tmp_path / "small"
+    bench.dump_outputs(str(small), {"ids": ids, "distances": dist, "counts": cnt}, 64, lambda m: None)
+    got = {n: np.load(small / (n + ".npy")) for n in ("ids", "distances", "counts")}
+    assert sorted(os.listdir(small)) == ["counts.npy", "distances.npy", "ids.npy"]
+    assert got["ids"].dtype == np.float64 and np.array_equal(got["ids"].astype(np.int64), ids)
+    assert got["distances"].dtype == np.float32 and np.array_equal(got["distances"], dist)
+    assert got["counts"].dtype == np.float64 and np.array_equal(got["counts"], cnt)
+    n = 3000
+    big = rng.standard_normal((n, 4096)).astype(np.float32)  # 48 MB of float32 -> 96 MB as two arrays
+    outs = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        bench.dump_outputs(str(d), {"x": big, "y": big.astype(np.float64)[:, :2048]}, n, lambda m: None)
+        assert sum(f.stat().st_size for f in d.iterdir()) <= bench.DUMP_LIMIT_BYTES
+        sel = np.load(d / "query_index.npy").astype(np.int64)
+        x = np.load(d / "x.npy")
+        assert 0 < len(sel) < n and np.array_equal(x, big[sel]) and np.array_equal(np.load(d / "y.npy"), big.astype(np.float64)[sel, :2048])
+        outs.append(sel)
+    assert np.array_equal(outs[0], outs[1])

@@ -4,8 +4,10 @@ exchange is torch.distributed all_gather over gloo (in the test: the package its
 carries no torch), the merge the package's own (the C ABI's pvs_merge_topk) and the merged page must equal the oracle's page over the
 whole corpus."""
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 import textwrap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -114,10 +116,15 @@ def test_three_ranks_over_the_package_rendezvous(tmp_path):
     """The torch-free control plane bench.py uses (panoptikon_amd/rendezvous.py): 3 ranks, star over a Unix socket."""
     script = tmp_path / "worker2.py"
     script.write_text(WORKER2)
-    sock = str(tmp_path / "ctl.sock")
-    procs = [subprocess.Popen([sys.executable, str(script)], env=dict(os.environ, RANK=str(r), WORLD_SIZE="3", PVS_CTL_SOCK=sock),
-                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(3)]
-    outs = [p.communicate(timeout=300) for p in procs]
+    # an AF_UNIX path holds at most 107 bytes and tmp_path under a deep TMPDIR can be longer: the socket lives in a short directory
+    sock_dir = tempfile.mkdtemp(prefix="pvs_", dir="/tmp")
+    sock = os.path.join(sock_dir, "ctl.sock")
+    try:
+        procs = [subprocess.Popen([sys.executable, str(script)], env=dict(os.environ, RANK=str(r), WORLD_SIZE="3", PVS_CTL_SOCK=sock),
+                                  stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for r in range(3)]
+        outs = [p.communicate(timeout=300) for p in procs]
+    finally:
+        shutil.rmtree(sock_dir, ignore_errors=True)
     for r, (p, (o, e)) in enumerate(zip(procs, outs)):
         assert p.returncode == 0, e[-3000:]
         assert f"rank{r}-ok" in o
