@@ -313,7 +313,16 @@ pvs_status pvs_search_bounded(pvs_index *idx, const void *queries, pvs_dtype que
  * the stream to wait on with pvs_wait (or pvs_sync for all of them).  At most 16 searches (the size of the
  * reference's read pool) can be in flight on one index: with none free the stream-ordered entry points
  * (this one, pvs_search_sharded_async) return PVS_ERR_STATE — pvs_wait one first — while the synchronous
- * ones block until a slot frees.  On a multi-device index the buffers live on devices[0]. */
+ * ones block until a slot frees.  On a multi-device index the buffers live on devices[0].
+ * Held tickets: two such searches on one index share one corpus pass (int8 rows: one 256-query pass B costs ~1.9 ms where two
+ * 128-query passes cost ~2.4).  A search is HELD when the index lives on one device with one stream (pvs_index_set_streams(1)),
+ * holds int8 rows, the batch has 9 to 128 queries and k fits the filter scan: its queries are read and prepared at this call, in
+ * stream order as before, and its passes wait for a partner.  The next such search with the same metric and k joins it and the
+ * pair is launched at once; every query's page is the one a 256-query batch gets (the same exact values and order), written to
+ * its own caller's buffers.  A held search is launched alone as soon as its ticket is waited on, another search on the index
+ * cannot join it, pvs_sync / pvs_index_get_profile / a mutation of the index / pvs_index_destroy is called, or the window
+ * expires: pvs_debug_set("join_us", N) microseconds, default 250; 0 never holds.  Each ticket is still waited on by itself and
+ * counts as one search in pvs_stats. */
 pvs_status pvs_search_device(pvs_index *idx, const void *d_queries, pvs_dtype query_dtype,
                              uint32_t batch, uint32_t k, pvs_metric metric, int64_t *d_out_ids,
                              float *d_out_dist, uint32_t *d_out_count, uint32_t *out_ticket);
@@ -670,7 +679,7 @@ pvs_status pvs_microbench(int32_t device, pvs_microbench_result *out);
 
 /* ------------------------------------------------------- test and tuning hooks */
 /* Not part of the product contract: the test suite and the measurement scripts use these to force a code path (and so compare
- * two product paths on the same input) or to sweep a tuning parameter.  Every knob is 0 in a process that never calls
+ * two product paths on the same input) or to sweep a tuning parameter.  Every knob but "join_us" is 0 in a process that never calls
  * pvs_debug_set, and the library reads NO environment variable to decide which algorithm answers (the only variable it looks at
  * is PVS_RCCL_PATH, a loader path for librccl).  Process-wide; set a knob while no search is in flight.
  *   "sample_div" N            pass A samples 1/N of the corpus            "sample_j_div" N     threshold = (k/N)-th sample value
@@ -696,7 +705,10 @@ pvs_status pvs_microbench(int32_t device, pvs_microbench_result *out);
  *                             all-reduce, the communicator's first collective), the shard exchange behind pvs_wait, the control
  *                             messages of the sharded fusion (default 180 s).  On expiry the communicator is aborted and the call
  *                             returns PVS_ERR_COMM naming the rank: create a new communicator
- *   "comm_fail_local" N       tests: the next N pvs_search_sharded_async calls of this process fail before their exchange */
+ *   "comm_fail_local" N       tests: the next N pvs_search_sharded_async calls of this process fail before their exchange
+ *   "join_us" N               pvs_search_device: how long a held search waits for a partner (default 250 us; 0: never held)
+ *   "joined_passes" / "joined_queries" / "join_alone_passes" / "join_window_launches"   (read-only counters) corpus passes two
+ *                             held searches shared and their queries; held searches launched alone, and of those by the window */
 pvs_status pvs_debug_set(const char *key, int64_t value);
 pvs_status pvs_debug_get(const char *key, int64_t *out_value);
 /* Stage digests of the process' last single-device pvs_rrf_search run under "rrf_digest": out[branch * 4 + stage], stage 0 = the

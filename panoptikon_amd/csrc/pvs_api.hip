@@ -29,7 +29,13 @@ const char *const g_dbg_names[PVS_DBG_COUNT] = {
     "direct_unit", "direct_static_pct", "direct_max_nq", "dense_full_sort", "dense_page_first", "no_flag_poll", "poll_late_pages",
     "no_exact_wide", "no_agg8", "no_dense2", "comm_timeout_s", "comm_fail_local",
     "no_float_certify", "float_certify_queries", "float_certify_rows", "float_certify_trace", "float_certify_no_fold",
+    "join_us", "joined_passes", "joined_queries", "join_alone_passes", "join_window_launches",
 };
+// the knobs whose default is not 0
+[[maybe_unused]] const bool g_dbg_defaults = [] {
+    g_dbg[PVS_DBG_JOIN_US].store(PVS_JOIN_US_DEFAULT);
+    return true;
+}();
 int dbg_key(const char *key) {
     if (!key) return -1;
     for (int i = 0; i < PVS_DBG_COUNT; i++)
@@ -558,6 +564,7 @@ PVS_EXPORT void pvs_index_destroy(pvs_index *ix) {
     if (!ix) return;
     if (is_multi(ix)) return multi_destroy(ix);
     (void)hipSetDevice(ix->device);
+    pvs_join_shutdown_(ix);  // (a held search is launched: its owner may still pvs_wait before destroying)
     (void)hipDeviceSynchronize();
     for (auto &c : ix->ctx) ctx_release(c);
     hipFree(ix->d_rows);
@@ -913,6 +920,7 @@ PVS_EXPORT pvs_status pvs_index_get_profile(pvs_index *ix, pvs_profile *out, int
         *out = tot;
         return PVS_OK;
     }
+    (void)pvs_join_flush_(ix);  // (the held search's spans belong to the profile of what was submitted)
     std::lock_guard<std::mutex> lk(ix->prof_mu);
     *out = ix->prof;
     out->struct_size = sizeof(pvs_profile);

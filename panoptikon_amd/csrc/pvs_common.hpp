@@ -95,8 +95,14 @@ enum PvsDbg {
     PVS_DBG_FLOAT_CERTIFY_ROWS,    // (a counter) candidate rows its exact stage rescanned, summed over chunks
     PVS_DBG_FLOAT_CERTIFY_TRACE,   // the certified route reports its decisions on stderr (candidate rows, bad queries, who answered)
     PVS_DBG_FLOAT_CERTIFY_NO_FOLD, // the certified route writes the key matrix (k_scan MODE 4) and folds in a second kernel also when the files are runs
+    PVS_DBG_JOIN_US,               // pvs_search_device: a search that may share its corpus pass is held this long for a partner (microseconds; 0: never held; default 250)
+    PVS_DBG_JOINED_PASSES,         // (a counter) corpus passes two held searches shared
+    PVS_DBG_JOINED_QUERIES,        // (a counter) queries of those passes
+    PVS_DBG_JOIN_ALONE_PASSES,     // (a counter) held searches launched alone (waited on, stream order, a writer, the window)
+    PVS_DBG_JOIN_WINDOW_LAUNCHES,  // (a counter) ... of them, by the window
     PVS_DBG_COUNT
 };
+constexpr int64_t PVS_JOIN_US_DEFAULT = 250;
 int64_t pvs_dbg(PvsDbg key);
 void pvs_dbg_add(PvsDbg key, int64_t v);  // counters among the keys
 

@@ -86,6 +86,7 @@ bool pvs_gate_excl_enter(pvs_index *ix) {
         return false;
     }
     const bool multi = is_multi(ix);
+    (void)pvs_join_flush_(ix);  // a held search (pvs_search_device.hip) starts now; draining its ticket below would launch it too
     std::unique_lock<std::mutex> lk(ix->mu);
     ix->gate_writers_waiting++;
     while (ix->gate_writer_active) ix->ctx_cv.wait(lk);  // writers take turns

@@ -5,13 +5,23 @@
 
 #include <algorithm>
 #include <cmath>
+#include <chrono>
 #include <condition_variable>
+#include <thread>
 
 #include "pvs_kernels.hpp"
 
 // ------------------------------------------------------------------- index
 struct PendingChunk {
     uint32_t qoff, nb;
+};
+
+// pass C of a joined pass: queries [at, nb) are the second caller's — pages, counts and host verdicts (FinalizeArgs.split)
+struct PageSplit {
+    uint32_t at;
+    int64_t *ids;
+    float *dist;
+    uint32_t *count, *h_flags, *h_seen;
 };
 
 struct TimedSpan {
@@ -81,6 +91,9 @@ struct SearchCtx {
     float *p_out_dist = nullptr;
     uint32_t *p_out_count = nullptr;
     bool p_fast = false;
+    // a held ticket of pvs_search_device whose group could not be launched: pvs_wait returns this instead of completing it
+    pvs_status j_status = PVS_OK;
+    std::string j_err;
     // sharded search: this rank's page, the gathered pages and flags
     pvs_comm *p_comm = nullptr;
     pvs_status p_local_status = PVS_OK;  // sharded search: this rank failed before the exchange and sent a failure record; pvs_wait returns this
@@ -263,6 +276,23 @@ struct pvs_index {
         uint32_t max_batch = 0;
         std::atomic<uint64_t> calls{0}, passes{0};
     } co;
+    // Held tickets of pvs_search_device (pvs_search_device.hip): a search that may share its corpus pass has its queries prepped at
+    // submit and waits here for a second one; the group is launched when it is full or when anything needs it (pvs_wait, a
+    // stream-ordered entry point, a writer, the window).  A second search joins by prepping its queries into the slots behind the
+    // first one's; the pair is launched at once (two tickets per pass at most).  Lock order: join.mu before mu.
+    struct {
+        std::mutex mu;
+        std::condition_variable cv;  // wakes the window thread (a new group, shutdown)
+        std::thread timer;           // started with the first held ticket
+        bool stop = false;
+        bool held = false;           // a ticket waits for a partner; its queries are prepped in slots [0, nb) of its context
+        uint32_t ticket = 0, nb = 0, k = 0;
+        int metric = 0;
+        int64_t *ids = nullptr;      // its caller's page
+        float *dist = nullptr;
+        uint32_t *count = nullptr;
+        std::chrono::steady_clock::time_point deadline;  // the window: launched alone at this point at the latest
+    } join;
     bool profiling = false;
     std::mutex prof_mu;
     pvs_profile prof{};
@@ -373,6 +403,12 @@ pvs_status search_host(pvs_index *ix, const void *queries, pvs_dtype qdtype, uin
 void ctx_done(pvs_index *ix, SearchCtx *c);
 pvs_status search_enqueue(pvs_index *ix, SearchCtx &c, const void *d_queries, int qdtype, uint32_t batch, uint32_t k, int metric,
                           int64_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, bool *used_fast, bool side_finalize = false);
+pvs_status prep_slot(pvs_index *ix, SearchCtx &c, const void *d_queries, int qdtype, uint32_t slot, uint32_t nb, uint32_t batch_pad, int metric);
+pvs_status enqueue_joined_pass(pvs_index *ix, SearchCtx &c, uint32_t nb, uint32_t k, int metric, int64_t *oid, float *od, uint32_t *oc,
+                               const PageSplit *split);
+// ---- pvs_search_device.hip: held tickets
+pvs_status pvs_join_flush_(pvs_index *ix);  // launches the held group, if any (stream-ordered entry points, writers)
+void pvs_join_shutdown_(pvs_index *ix);     // launches it and stops the window thread (pvs_index_destroy)
 pvs_status search_fallbacks(pvs_index *ix, SearchCtx &c, const void *d_queries, int qdtype, uint32_t batch, uint32_t k, int metric,
                             int64_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count);
 pvs_status ctx_reserve_local_pages(SearchCtx &c, uint32_t batch, uint32_t k);

@@ -194,6 +194,12 @@ struct FinalizeArgs {
     // pinned host mirrors of need_dense / cand_seen: the kernel writes its verdicts straight into host memory, so that no copy
     // kernel (4-5 us each, plus a launch gap) follows every search just to fetch two words per query
     uint32_t *h_flags = nullptr, *h_seen = nullptr;
+    // a pass shared by two callers (pvs_search_device, joined tickets): queries [split, batch) belong to the second one — their
+    // pages, counts and host verdicts go to its buffers at q - split; the device words (need_dense, cand_seen) stay at q
+    uint32_t split = UINT32_MAX;
+    int64_t *out_ids2 = nullptr;
+    float *out_dist2 = nullptr;
+    uint32_t *out_count2 = nullptr, *h_flags2 = nullptr, *h_seen2 = nullptr;
     // second sort key (pvs_index_set_order_keys): ties on the distance are ordered by tie rank instead of by row
     const uint32_t *trank = nullptr, *tinv = nullptr;
     // Optional global-memory work area: with it (int8 rows) pass C keeps its bound keys, survivor list and large sorts in HBM/L2

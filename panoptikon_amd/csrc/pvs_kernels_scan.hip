@@ -317,6 +317,10 @@ struct FinK {
     int null_ok;                   // short pages may be completed from the NULL list (flag 3)
     uint32_t *h_flags, *h_seen;    // pinned host mirrors of need_dense / cand_seen (FinalizeArgs.h_flags), or nullptr
     const uint32_t *trank, *tinv;  // second sort key: tie rank of a row and its inverse (FinalizeArgs.trank)
+    uint32_t split;                // queries >= split: the second caller's buffers (FinalizeArgs.split)
+    int64_t *out_ids2;
+    float *out_dist2;
+    uint32_t *out_count2, *h_flags2, *h_seen2;
 };
 
 constexpr int FIN_QMAX = 8192;  // bytes of LDS for the query vector the rerank reads (dims beyond that read it from global memory)
@@ -360,17 +364,23 @@ __global__ __launch_bounds__(256) void k_finalize(FinK a) {
 #define FIN_STAMP(i) do { } while (0)
 #endif
     FIN_STAMP(0);
-    int64_t *oid = a.out_ids + (size_t)q * a.k;
-    float *od = a.out_dist + (size_t)q * a.k;
+    // the caller this query's page belongs to (a joined pass: FinalizeArgs.split) and its slot there
+    const bool second = q >= a.split;
+    const uint32_t qo = second ? q - a.split : q;
+    uint32_t *const out_count = second ? a.out_count2 : a.out_count;
+    uint32_t *const h_flags = second ? a.h_flags2 : a.h_flags;
+    uint32_t *const h_seen = second ? a.h_seen2 : a.h_seen;
+    int64_t *oid = (second ? a.out_ids2 : a.out_ids) + (size_t)qo * a.k;
+    float *od = (second ? a.out_dist2 : a.out_dist) + (size_t)qo * a.k;
     // a query that makes every distance NULL (zero / NaN-bearing): the whole page is the head of ALL rows in tie order — the
     // NULL-tail step writes it (flag 3); nothing was emitted for it (k_kth gave it T = -inf)
     if (a.null_ok && !a.flat_cnt && pvs_query_all_null(a.metric, a.qinfo[q].bb)) {
         if (tid == 0) {
             a.need_dense[q] = 3;
-            if (a.h_flags) a.h_flags[q] = 3;
-            a.out_count[q] = 0;
+            if (h_flags) h_flags[qo] = 3;
+            out_count[qo] = 0;
             if (a.cand_seen) a.cand_seen[q] = 0;
-            if (a.h_seen) a.h_seen[q] = 0;
+            if (h_seen) h_seen[qo] = 0;
         }
         return;
     }
@@ -489,7 +499,7 @@ __global__ __launch_bounds__(256) void k_finalize(FinK a) {
     }
     FIN_STAMP(1);
     if (tid == 0 && a.cand_seen) a.cand_seen[q] = cnt;
-    if (tid == 0 && a.h_seen) a.h_seen[q] = cnt;
+    if (tid == 0 && h_seen) h_seen[qo] = cnt;
     const uint64_t want = a.k < a.n_rows ? a.k : a.n_rows;
     // a short page can be completed from the index's NULL list when every row with a comparable key was emitted (T = +inf)
     // ... and the query is an ordinary one (a finite, for cosine non-zero, norm): a query with an infinite component turns rows
@@ -499,8 +509,8 @@ __global__ __launch_bounds__(256) void k_finalize(FinK a) {
     if (cnt > a.cand_cap || (cnt < want && !can_complete)) {  // overflowed, or NULL-distance rows are needed to fill the page
         if (tid == 0) {
             a.need_dense[q] = seg_overflow_only ? 2 : 1;
-            if (a.h_flags) a.h_flags[q] = seg_overflow_only ? 2 : 1;
-            a.out_count[q] = 0;
+            if (h_flags) h_flags[qo] = seg_overflow_only ? 2 : 1;
+            out_count[qo] = 0;
         }
         return;
     }
@@ -531,8 +541,8 @@ __global__ __launch_bounds__(256) void k_finalize(FinK a) {
     if (a.thr && want == a.k && !(kappa <= a.thr[q])) {
         if (tid == 0) {
             a.need_dense[q] = 1;
-            if (a.h_flags) a.h_flags[q] = 1;
-            a.out_count[q] = 0;
+            if (h_flags) h_flags[qo] = 1;
+            out_count[qo] = 0;
         }
         return;
     }
@@ -551,8 +561,8 @@ __global__ __launch_bounds__(256) void k_finalize(FinK a) {
     if (m > PVS_SURV_CAP) {  // massive near-ties: let the dense path answer
         if (tid == 0) {
             a.need_dense[q] = 1;
-            if (a.h_flags) a.h_flags[q] = 1;
-            a.out_count[q] = 0;
+            if (h_flags) h_flags[qo] = 1;
+            out_count[qo] = 0;
         }
         return;
     }
@@ -666,8 +676,8 @@ __global__ __launch_bounds__(256) void k_finalize(FinK a) {
     if (tail && !can_complete) {
         if (tid == 0) {
             a.need_dense[q] = 1;
-            if (a.h_flags) a.h_flags[q] = 1;
-            a.out_count[q] = 0;
+            if (h_flags) h_flags[qo] = 1;
+            out_count[qo] = 0;
         }
         return;
     }
@@ -682,9 +692,9 @@ __global__ __launch_bounds__(256) void k_finalize(FinK a) {
         }
     }
     if (tid == 0) {
-        a.out_count[q] = nout;
+        out_count[qo] = nout;
         a.need_dense[q] = tail ? 3 : 0;
-        if (a.h_flags) a.h_flags[q] = tail ? 3 : 0;
+        if (h_flags) h_flags[qo] = tail ? 3 : 0;
     }
 }
 
@@ -709,6 +719,12 @@ hipError_t pvs_launch_finalize(const FinalizeArgs &f, hipStream_t s) {
     k.null_ok = f.null_ok;
     k.h_flags = f.h_flags;
     k.h_seen = f.h_seen;
+    k.split = f.split;
+    k.out_ids2 = f.out_ids2;
+    k.out_dist2 = f.out_dist2;
+    k.out_count2 = f.out_count2;
+    k.h_flags2 = f.h_flags2;
+    k.h_seen2 = f.h_seen2;
     k.trank = f.trank;
     k.tinv = f.tinv;
     k.cand = f.cand;

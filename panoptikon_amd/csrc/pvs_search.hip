@@ -63,8 +63,10 @@ pvs_status prep_chunk(pvs_index *ix, SearchCtx &c, const void *d_queries, int qd
 // back with need_dense == 2 — a candidate segment overflowed although the query's candidates fit one list (ties clustered in a
 // few tile streams) — with pass B appending to per-query flat lists through atomic counters; the other queries' thresholds
 // are voided so that they emit nothing, and pass C finalises the handed-back ones only.
+// split: a joined pass (pvs_search_device) — pass C writes the pages of queries [split->at, nb) into the second caller's buffers.
 static pvs_status enqueue_fast_chunk(pvs_index *ix, SearchCtx &c, uint32_t qoff, uint32_t nb, uint32_t batch_pad, uint32_t k, int metric,
-                                     int64_t *oid, float *od, uint32_t *oc, bool flat_rerun, bool side = false, hipStream_t prelude = nullptr) {
+                                     int64_t *oid, float *od, uint32_t *oc, bool flat_rerun, bool side = false, hipStream_t prelude = nullptr,
+                                     const PageSplit *split = nullptr) {
     // prelude: pass A and the k-th select go to that stream (the caller queued the query prep there), pass B waits for them
     if ((ix->multi_stream || side || pvs_dbg(PVS_DBG_FORCE_LIGHT_FINALIZE)) && !pvs_dbg(PVS_DBG_NO_LIGHT_FINALIZE)) PVS_TRY(ctx_fin_buffers(c));  // (first such search of the context)
     ScanArgs a;
@@ -204,6 +206,14 @@ static pvs_status enqueue_fast_chunk(pvs_index *ix, SearchCtx &c, uint32_t qoff,
     if (flat_rerun) f.flat_cnt = c.d_flat_cnt;
     f.h_flags = c.h_need_dense + qoff;  // (hipHostMalloc: the same address on the device)
     f.h_seen = c.h_need_dense + c.flags_cap + qoff;
+    if (split) {
+        f.split = split->at;
+        f.out_ids2 = split->ids;
+        f.out_dist2 = split->dist;
+        f.out_count2 = split->count;
+        f.h_flags2 = split->h_flags;
+        f.h_seen2 = split->h_seen;
+    }
     if (k_sel < k) f.thr = c.d_thr;  // thresholds below the k-th sample value: pass C certifies them
     f.thr_all = c.d_thr;
     // pages that end in NULL rows are completed from the index's NULL list of the metric (search_fallbacks, flag 3) when that set
@@ -299,6 +309,29 @@ pvs_status enqueue_direct(pvs_index *ix, SearchCtx &c, const void *d_queries, in
     HIP_TRY(pvs_launch_direct_topk(d, c.stream));
     ix->direct_queries += batch;
     pvs_dbg_add(PVS_DBG_DIRECT_QUERIES, batch);
+    return PVS_OK;
+}
+
+// Query prep into slots [slot, slot + batch_pad) of context c: the second caller of a joined pass puts its queries behind the
+// first one's (rows past nb are zeroed padding, as prep_chunk pads).
+pvs_status prep_slot(pvs_index *ix, SearchCtx &c, const void *d_queries, int qdtype, uint32_t slot, uint32_t nb, uint32_t batch_pad, int metric) {
+    if (slot + batch_pad > PVS_SCAN_MAX_BATCH || slot + nb > c.flags_cap) return pvs_fail(PVS_ERR_INVALID_ARG, "query slots [%u, +%u) outside the context", slot, batch_pad);
+    const size_t qesz = ix->dtype == PVS_I8 ? 1 : 4;
+    HIP_TRY(pvs_launch_prep_queries((int)ix->dtype, qdtype, d_queries, nb, batch_pad, ix->dim, ix->stride, ix->scale, metric,
+                                    c.d_qmat + (size_t)slot * ix->stride, c.d_qexact + (size_t)slot * ix->dim * qesz, c.d_qinfo + slot,
+                                    c.d_need_dense + slot, c.stream));
+    return PVS_OK;
+}
+
+// Passes A / B / C of a held group (pvs_search_device.hip): nb prepared queries in context c, the first caller's pages to oid / od /
+// oc, the second caller's (split, or nullptr for a lone ticket) to its own buffers.  c.done is recorded behind pass C.
+pvs_status enqueue_joined_pass(pvs_index *ix, SearchCtx &c, uint32_t nb, uint32_t k, int metric, int64_t *oid, float *od, uint32_t *oc,
+                               const PageSplit *split) {
+    const uint32_t batch_pad = nb <= 32 ? 32 : nb <= 64 ? 64 : nb <= 128 ? 128 : 256;
+    const bool side = !ix->multi_stream && c.stream == ix->search_stream && !pvs_dbg(PVS_DBG_NO_SIDE_FINALIZE);
+    c.side_finalize = false;
+    PVS_TRY(enqueue_fast_chunk(ix, c, 0, nb, batch_pad, k, metric, oid, od, oc, false, side, nullptr, split));
+    HIP_TRY(hipEventRecord(c.done, c.side_finalize ? ix->fin_stream : c.stream));
     return PVS_OK;
 }
 

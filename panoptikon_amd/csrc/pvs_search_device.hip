@@ -8,6 +8,174 @@
 
 #include "pvs_index.hpp"
 
+// ---- held tickets: two searches on one index share one corpus pass
+// The int8 pass B streams the corpus once for up to 256 queries (k_scan_wide) in ~1.9 ms, against ~1.2 ms for 128: a pipelined
+// caller's two batches of 128 cost 2.4 ms as two passes and 1.9 ms as one.  A search that may share its pass (join_applies) has
+// its queries prepped at submit, in stream order as before, and is HELD (pvs_index::join); the next compatible search preps its
+// queries into the slots behind them and launches the pair: pass A, the k-th select and pass B over all of them, pass C writing
+// every query's page, count and verdict into its own caller's buffers (FinalizeArgs.split).  Each ticket then completes on its
+// own: its done event is recorded behind the shared pass C, its fallbacks (the queries pass C handed back) run at its pvs_wait
+// over its own queries.  Every page is the one the same passes give a 256-query batch: the same exact values and order.
+// A held group is launched alone when its ticket is waited on, when anything needs stream order (a search that is not held,
+// pvs_sync, the profile, a writer at the gate, destroy), or when the window (pvs_debug "join_us", 0 = never hold) expires.
+static bool join_applies(pvs_index *ix, uint32_t batch, uint32_t k) {
+    if (pvs_dbg(PVS_DBG_JOIN_US) <= 0 || ix->multi_stream || ix->dtype != PVS_I8 || ix->n == 0) return false;
+    const uint32_t pass_max = pvs_scan_max_batch((int)ix->dtype, ix->stride / PVS_KSLAB_BYTES);
+    // (1..8 queries: the one-launch search or a latency-bound caller — never held)
+    return batch > PVS_DIRECT_MAX_NQ && 2 * batch <= pass_max && pass_max == PVS_SCAN_MAX_BATCH && fast_path_ok(ix, k);
+}
+static uint32_t pass_pad(uint32_t nb) { return nb <= 32 ? 32 : nb <= 64 ? 64 : nb <= 128 ? 128 : 256; }
+
+struct JoinPartner {  // the search that completes a held group
+    uint32_t ticket, nb;
+    int64_t *ids;
+    float *dist;
+    uint32_t *count;
+};
+// (join.mu held) launches the held group, with the partner's queries (already prepped behind the held ones) if there is one.  A
+// failure is parked in the tickets' contexts (j_status): their pvs_wait reports it.
+static pvs_status join_launch_locked(pvs_index *ix, const JoinPartner *p) {
+    auto &j = ix->join;
+    if (!j.held) return PVS_OK;
+    j.held = false;
+    SearchCtx &c = ix->ctx[j.ticket];
+    SearchCtx *m = p ? &ix->ctx[p->ticket] : nullptr;
+    const uint32_t nb = j.nb + (p ? p->nb : 0);
+    auto body = [&]() -> pvs_status {
+        HIP_TRY(hipSetDevice(ix->device));
+        PageSplit sp{};
+        if (m) sp = PageSplit{j.nb, p->ids, p->dist, p->count, m->h_need_dense, m->h_need_dense + m->flags_cap};
+        PVS_TRY(enqueue_joined_pass(ix, c, nb, j.k, j.metric, j.ids, j.dist, j.count, m ? &sp : nullptr));
+        if (m) HIP_TRY(hipEventRecord(m->done, c.side_finalize ? ix->fin_stream : c.stream));
+        return PVS_OK;
+    };
+    const pvs_status st = body();
+    if (st == PVS_OK) {
+        pvs_dbg_add(m ? PVS_DBG_JOINED_PASSES : PVS_DBG_JOIN_ALONE_PASSES, 1);
+        if (m) pvs_dbg_add(PVS_DBG_JOINED_QUERIES, nb);
+        return PVS_OK;
+    }
+    const std::string why = pvs_last_error();
+    (void)hipStreamSynchronize(c.stream);
+    (void)hipStreamSynchronize(ix->fin_stream);
+    c.j_status = st;
+    c.j_err = why;
+    if (m) {
+        m->j_status = st;
+        m->j_err = why;
+    }
+    return st;
+}
+pvs_status pvs_join_flush_(pvs_index *ix) {
+    if (!ix || is_multi(ix)) return PVS_OK;
+    std::lock_guard<std::mutex> lk(ix->join.mu);
+    return join_launch_locked(ix, nullptr);
+}
+// the window: a held group nobody joins or waits for is launched alone when its deadline passes
+static void join_window(pvs_index *ix) {
+    auto &j = ix->join;
+    (void)hipSetDevice(ix->device);
+    std::unique_lock<std::mutex> lk(j.mu);
+    while (!j.stop) {
+        if (!j.held) {
+            j.cv.wait(lk);
+            continue;
+        }
+        const auto dl = j.deadline;
+        if (j.cv.wait_until(lk, dl) == std::cv_status::timeout && j.held && j.deadline == dl) {
+            (void)join_launch_locked(ix, nullptr);
+            pvs_dbg_add(PVS_DBG_JOIN_WINDOW_LAUNCHES, 1);
+        }
+    }
+}
+void pvs_join_shutdown_(pvs_index *ix) {
+    auto &j = ix->join;
+    {
+        std::lock_guard<std::mutex> lk(j.mu);
+        (void)join_launch_locked(ix, nullptr);
+        j.stop = true;
+    }
+    j.cv.notify_all();
+    if (j.timer.joinable()) j.timer.join();
+}
+
+// a search that may share its pass: prepped now, held or joined (above)
+static pvs_status search_device_held(pvs_index *ix, const void *d_queries, pvs_dtype qdtype, uint32_t batch, uint32_t k, pvs_metric metric,
+                                     int64_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count, uint32_t *out_ticket) {
+    uint32_t t;
+    SearchCtx *c = ctx_acquire(ix, &t, false);
+    if (!c) return PVS_ERR_STATE;
+    c->j_status = PVS_OK;
+    c->j_err.clear();
+    pvs_status st = ctx_prepare(ix, *c, batch, k, false);
+    if (st == PVS_OK) st = pvs_ensure_null_rows(ix);  // (as search_enqueue: one pass over |a|^2 per index state)
+    auto &j = ix->join;
+    bool notify = false;
+    if (st == PVS_OK) {
+        std::lock_guard<std::mutex> lk(j.mu);
+        const uint32_t pass_max = pvs_scan_max_batch((int)ix->dtype, ix->stride / PVS_KSLAB_BYTES);
+        // (the order keys and tie ranks of the held search are this one's: a writer launches a held group before it changes them)
+        const bool fits = j.held && j.k == k && j.metric == (int)metric && j.nb + batch <= pass_max;
+        if (j.held && !fits) (void)join_launch_locked(ix, nullptr);  // an incompatible group goes first (stream order)
+        if (j.held) {
+            // join: the queries go into the slots behind the held ones (prep pads to the pair's pass width), the pair is launched
+            const uint32_t pad = pass_pad(j.nb + batch);
+            st = prep_slot(ix, ix->ctx[j.ticket], d_queries, qdtype, j.nb, batch, pad - j.nb, metric);
+            if (st == PVS_OK) {
+                const JoinPartner p{t, batch, d_out_ids, d_out_dist, d_out_count};
+                (void)join_launch_locked(ix, &p);  // (a failure is this ticket's too: its pvs_wait reports it)
+            } else {
+                (void)join_launch_locked(ix, nullptr);
+            }
+        } else {
+            st = prep_slot(ix, *c, d_queries, qdtype, 0, batch, pass_pad(batch), metric);
+            if (st == PVS_OK) {
+                j.held = true;
+                j.ticket = t;
+                j.nb = batch;
+                j.k = k;
+                j.metric = (int)metric;
+                j.ids = d_out_ids;
+                j.dist = d_out_dist;
+                j.count = d_out_count;
+                j.deadline = std::chrono::steady_clock::now() + std::chrono::microseconds(pvs_dbg(PVS_DBG_JOIN_US));
+                notify = true;
+                if (!j.timer.joinable() && !j.stop) {
+                    try {
+                        j.timer = std::thread(join_window, ix);
+                    } catch (...) {  // no window thread: never leave a search held
+                        (void)join_launch_locked(ix, nullptr);
+                        notify = false;
+                    }
+                }
+            }
+        }
+    }
+    if (notify) j.cv.notify_all();
+    if (st != PVS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        ctx_done(ix, c);
+        return st;
+    }
+    c->p_queries = d_queries;
+    c->p_qdtype = qdtype;
+    c->p_metric = metric;
+    c->p_batch = batch;
+    c->p_k = k;
+    c->p_out_ids = d_out_ids;
+    c->p_out_dist = d_out_dist;
+    c->p_out_count = d_out_count;
+    c->p_fast = true;
+    c->p_comm = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        c->pending = true;  // (published after every p_* field: a writer draining the index reads them)
+    }
+    ix->searches++;
+    *out_ticket = t;
+    return PVS_OK;
+}
+
 PVS_EXPORT pvs_status pvs_search_device(pvs_index *ix, const void *d_queries, pvs_dtype qdtype, uint32_t batch, uint32_t k,
                                         pvs_metric metric, int64_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count,
                                         uint32_t *out_ticket) {
@@ -17,9 +185,13 @@ PVS_EXPORT pvs_status pvs_search_device(pvs_index *ix, const void *d_queries, pv
     if (!d_out_ids || !d_out_dist || !d_out_count || !out_ticket) return pvs_fail(PVS_ERR_INVALID_ARG, "null output");
     if (batch == 0) return pvs_fail(PVS_ERR_INVALID_ARG, "empty batch");
     HIP_TRY(hipSetDevice(ix->device));
+    if (join_applies(ix, batch, k)) return search_device_held(ix, d_queries, qdtype, batch, k, metric, d_out_ids, d_out_dist, d_out_count, out_ticket);
+    (void)pvs_join_flush_(ix);  // a search that is not held goes behind the held one (a launch failure is the held ticket's)
     uint32_t t;
     SearchCtx *c = ctx_acquire(ix, &t, false);
     if (!c) return PVS_ERR_STATE;
+    c->j_status = PVS_OK;
+    c->j_err.clear();
     pvs_status st = ctx_prepare(ix, *c, batch, k, false);
     bool fast = false;
     if (st == PVS_OK) st = search_enqueue(ix, *c, d_queries, qdtype, batch, k, metric, d_out_ids, d_out_dist, d_out_count, &fast, true);
@@ -30,10 +202,6 @@ PVS_EXPORT pvs_status pvs_search_device(pvs_index *ix, const void *d_queries, pv
         ctx_done(ix, c);
         return st;
     }
-    {
-        std::lock_guard<std::mutex> lk(ix->mu);
-        c->pending = true;
-    }
     c->p_queries = d_queries;
     c->p_qdtype = qdtype;
     c->p_metric = metric;
@@ -43,6 +211,11 @@ PVS_EXPORT pvs_status pvs_search_device(pvs_index *ix, const void *d_queries, pv
     c->p_out_dist = d_out_dist;
     c->p_out_count = d_out_count;
     c->p_fast = fast;
+    c->p_comm = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(ix->mu);
+        c->pending = true;  // (published after every p_* field: a writer draining the index reads them)
+    }
     ix->searches++;
     *out_ticket = t;
     return PVS_OK;
@@ -71,6 +244,15 @@ pvs_status pvs_ticket_complete_(pvs_index *ix, uint32_t ticket) {
 }
 static pvs_status ticket_complete_body(pvs_index *ix, SearchCtx *c) {
     HIP_TRY(hipSetDevice(ix->device));
+    if (!c->p_comm) {  // a held ticket: its group is launched now (alone)
+        std::lock_guard<std::mutex> lk(ix->join.mu);
+        if (ix->join.held && &ix->ctx[ix->join.ticket] == c) (void)join_launch_locked(ix, nullptr);
+    }
+    if (c->j_status != PVS_OK) {  // its pass could not be launched (join_launch_locked)
+        const pvs_status js = c->j_status;
+        c->j_status = PVS_OK;
+        return pvs_fail(js, "%s", c->j_err.c_str());
+    }
     pvs_status st = PVS_OK;
     if (c->p_comm) {  // behind a collective: the other ranks may never arrive — bounded (pvs_comm.hip)
         st = pvs_comm_wait_event_(c->p_comm, c->done, "shard exchange (all-gather + merge)");
@@ -191,10 +373,6 @@ PVS_EXPORT pvs_status pvs_search_sharded_async(pvs_index *ix, pvs_comm *comm, co
     bool exchanged = false;  // the all-gather of this search has been queued (a failure after that point is every rank's failure)
     hipStream_t cs = ix->comm_stream;
     auto park = [&](bool fast) {  // the search is in flight: pvs_wait completes it
-        {
-            std::lock_guard<std::mutex> lk(ix->mu);
-            c->pending = true;
-        }
         c->p_comm = comm;
         c->p_queries = d_queries;
         c->p_qdtype = qdtype;
@@ -208,6 +386,8 @@ PVS_EXPORT pvs_status pvs_search_sharded_async(pvs_index *ix, pvs_comm *comm, co
         c->p_final_dist = d_out_dist;
         c->p_final_count = d_out_count;
         c->p_fast = fast;
+        std::lock_guard<std::mutex> lk(ix->mu);
+        c->pending = true;  // (published after every p_* field: a writer draining the index reads them)
     };
     auto buffers = [&]() -> pvs_status {
         PVS_TRY(ctx_prepare(ix, *c, batch, k, false));
@@ -310,6 +490,7 @@ PVS_EXPORT pvs_status pvs_search_sharded(pvs_index *ix, pvs_comm *comm, const vo
 PVS_EXPORT pvs_status pvs_sync(pvs_index *ix) {
     if (!ix) return pvs_fail(PVS_ERR_INVALID_ARG, "null index");
     if (is_multi(ix)) return multi_sync(ix);
+    (void)pvs_join_flush_(ix);  // (a launch failure is reported by that ticket's pvs_wait below)
     pvs_status st = PVS_OK;
     for (uint32_t i = 0; i < NCTX; i++) {
         bool live;
