@@ -473,6 +473,16 @@ typedef struct pvs_rrf_branch {
 } pvs_rrf_branch;
 pvs_status pvs_rrf_search(const pvs_rrf_branch *branches, uint32_t n_branches, uint32_t k, int64_t *out_groups,
                           double *out_scores, uint32_t *out_count);
+/* A batch of composed queries: branches[b].query points to `batch` consecutive query vectors in the branch's query_dtype; every
+ * other field applies to every query of the batch.  Row j of the outputs ([batch][k] groups and scores, [batch] counts) is bit for
+ * bit what pvs_rrf_search returns when each branch's query is its j-th vector (unused slots -1 / NaN, the order-key tie rule
+ * included).  Each branch is scored for up to 32 queries per corpus pass (fewer when device memory is short); the first fusion
+ * round runs for the whole chunk at once, and each query then continues over its own columns where it must.  Same checks and statuses as pvs_rrf_search; batch = 0 writes nothing.  Every branch's index is held
+ * shared for the whole call.  Multi-device branches are answered one composed query after the other: correct, not faster.
+ * pvs_rrf_last_path() afterwards: 2 if any query of the batch needed the full ranking, else 1.  pvs_debug_rrf_digests covers
+ * pvs_rrf_search only. */
+pvs_status pvs_rrf_search_batch(const pvs_rrf_branch *branches, uint32_t n_branches, uint32_t batch, uint32_t k, int64_t *out_groups,
+                                double *out_scores, uint32_t *out_counts);
 /* The steps of pvs_rrf_search's bounded fusion, for hosts that shard a branch BY GROUP over several GPUs or ranks (every row of a
  * group on one shard; configs[4] of BASELINE.json).  One pvs_rrf_cols = one branch scored on one shard: every row's exact
  * distance, the per-group aggregate (f64) and its window key — an order-preserving u64 with the window's NULL placement and

@@ -8,7 +8,7 @@ from ._lib import (AGG_AVG, AGG_MAX, AGG_MIN, AGG_NONE, COSINE, DEVICE, F16, F32
                    INDEX_EXACT, INDEX_QUANT, L2, PvsError, debug_get, debug_set, lib)
 from .index import DeviceBuffer, VectorIndex, absmax, device_count, microbench, quantize_int8
 from .host import (aggregate, artifact_scale, coalesce_ranks, coalesce_values, sort_bounds, embedding_from_npy_bytes, extract_embeddings, merge_group_pages, merge_topk,
-                   resolve_vector_quant, row_number, rrf_fuse, rrf_search, scale_artifact, scale_from_absmax)
+                   resolve_vector_quant, row_number, rrf_fuse, rrf_search, rrf_search_batch, scale_artifact, scale_from_absmax)
 
 from .rendezvous import LocalRendezvous
 from .host import RrfCols

@@ -125,6 +125,7 @@ SYMBOLS = {
     "pvs_device_synchronize": (_i32, [_i32]),
     "pvs_device_mem_info": (_i32, [_i32, _vp, _vp]),
     "pvs_rrf_search": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp]),
+    "pvs_rrf_search_batch": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "pvs_rrf_last_path": (_i32, []),
     "pvs_rrf_search_sharded": (_i32, [C.POINTER(RrfBranch), _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "pvs_rrf_cols_create": (_i32, [C.POINTER(RrfBranch), C.POINTER(_vp)]),

@@ -447,6 +447,16 @@ pvs_status aggregate_and_rank(pvs_index *ix, SearchCtx &c, const float *d_m, uin
 // not wait for them (the caller looks at it after its own synchronisation and, if raised, calls again with inorder_only)
 pvs_status dense_chunk(pvs_index *ix, SearchCtx &c, uint32_t nb, uint32_t batch_pad, int metric, float *d_out, uint32_t *h_flag = nullptr,
                        bool inorder_only = false);
+// queries per dense chunk so that the [n][nb] f32 matrix stays <= 2 GiB
+uint32_t dense_chunk_queries(const pvs_index *ix, uint32_t batch);
+// the one-pass per-item scorer (k_scan MODE 3, or the v_dot4 fold for <= 4 queries) can serve this chunk: int8 rows inside the closed
+// form's range, groups that are runs of rows
+bool fused_groups_ok(const pvs_index *ix, uint32_t nb, const uint8_t *d_mask, const float *d_w);
+// one corpus pass over the nb queries prepared in c, enqueued: d_vals_t [n_groups][nb] = every group's aggregate.  An L2 sum that left
+// the closed form's range raises word 8 of c.h_io (the caller scores in order instead).  d_m: an [n][nb] matrix for the rows of
+// tile-crossing groups
+pvs_status fused_group_chunk(pvs_index *ix, SearchCtx &c, uint32_t nb, uint32_t batch_pad, int metric, int agg, const float *d_w, const uint8_t *d_mask,
+                             float *d_m, double *d_vals_t);
 pvs_status search_groups_impl(pvs_index *ix, const void *queries, pvs_dtype qdtype, uint32_t batch, uint32_t k, pvs_metric metric,
                               pvs_agg agg, const float *row_weights, const uint8_t *mask, pvs_space mask_space, int64_t *out_groups,
                               double *out_values, uint32_t *out_count);

@@ -192,7 +192,7 @@ pvs_status dense_chunk(pvs_index *ix, SearchCtx &c, uint32_t nb, uint32_t batch_
 }
 
 // queries per dense chunk so that the [n][nb] f32 matrix stays <= 2 GiB
-static uint32_t dense_chunk_queries(const pvs_index *ix, uint32_t batch) {
+uint32_t dense_chunk_queries(const pvs_index *ix, uint32_t batch) {
     const uint64_t cap = (1ull << 31) / (4 * std::max<uint64_t>(ix->n, 1));
     return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>({cap, (uint64_t)PVS_MAX_BATCH, (uint64_t)batch}));
 }
@@ -580,7 +580,7 @@ PVS_EXPORT pvs_status pvs_search_groups_filtered(pvs_index *ix, const void *quer
 
 // Can the fused per-item scorer serve this chunk?  int8 rows inside the closed form's range on a row pitch k_scan has an instance
 // for, groups that are runs of rows, per-row arrays the scalar loads of the fold can read in aligned 32-row pieces.
-static bool fused_groups_ok(const pvs_index *ix, uint32_t nb, const uint8_t *d_mask, const float *d_w) {
+bool fused_groups_ok(const pvs_index *ix, uint32_t nb, const uint8_t *d_mask, const float *d_w) {
     if (pvs_dbg(PVS_DBG_NO_FUSED_AGG) || !ix->groups_are_runs || !ix->d_tile_grp) return false;
     if (ix->dtype != PVS_I8 || !pvs_scan_supported(PVS_I8, ix->stride / PVS_KSLAB_BYTES) || (uint64_t)ix->dim * 127 * 127 >= (1u << 24)) return false;
     if (((uintptr_t)d_mask & 3u) || ((uintptr_t)d_w & 3u)) return false;
@@ -590,7 +590,7 @@ static bool fused_groups_ok(const pvs_index *ix, uint32_t nb, const uint8_t *d_m
 // One corpus pass over the queries prepared in c, enqueued: d_vals_t [n_groups][nb] = every group's aggregate.  An L2 sum that left
 // the closed form's range raises word 8 of c.h_io (the caller scores in order instead).  d_m: the [n][nb] matrix the rows of
 // tile-crossing groups go through.
-static pvs_status fused_group_chunk(pvs_index *ix, SearchCtx &c, uint32_t nb, uint32_t batch_pad, int metric, int agg, const float *d_w, const uint8_t *d_mask,
+pvs_status fused_group_chunk(pvs_index *ix, SearchCtx &c, uint32_t nb, uint32_t batch_pad, int metric, int agg, const float *d_w, const uint8_t *d_mask,
                                     float *d_m, double *d_vals_t) {
     if (nb <= 4 && !pvs_dbg(PVS_DBG_NO_DIRECT_SCORE)) {
         // one to four queries: the v_dot4 stream with the fold in its tile epilogue (pvs_score_direct.hip) — the matrix-core scorer

@@ -365,6 +365,13 @@ size_t pvs_rrf_round_device_work_bytes(uint32_t nb);
 size_t pvs_rrf_round_device_out_bytes(uint32_t nb, uint32_t k);
 hipError_t pvs_rrf_round_device(const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb, const PvsRrfParams &p,
                                 uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s);
+// the same round for nq queries of a batch, every step one launch for the chunk: d_keys[q * nb + b]; work and pinned output blocks
+// of the two sizes below; query q's output at h_out + q * pvs_rrf_round_device_out_stride
+size_t pvs_rrf_round_device_out_stride(uint32_t nb, uint32_t k);
+size_t pvs_rrf_round_device_batch_work_bytes(uint32_t nb, uint32_t nq);
+size_t pvs_rrf_round_device_batch_out_bytes(uint32_t nb, uint32_t k, uint32_t nq);
+hipError_t pvs_rrf_round_device_batch(uint32_t nq, const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb,
+                                      const PvsRrfParams &p, uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s);
 void pvs_rrf_round_device_result(const uint8_t *h_out, uint32_t nb, uint32_t k, uint32_t *flags, uint32_t *R, uint32_t *m, uint32_t *n_out, const int64_t **groups,
                                  const double **scores);
 // order-independent 64-bit digest of n words of 4 or 8 bytes (synchronous; race hunting, pvs_debug_rrf_digests)
@@ -372,6 +379,10 @@ pvs_status pvs_digest_device(const void *d, uint64_t n, int word_bytes, uint64_t
 // bounded fusion: window keys of every group of a branch, a sample of them, the page of groups at or below a key, the keys of
 // given groups, and how many groups stand strictly before each of a handful of candidates (one counting pass over the keys)
 pvs_status pvs_rrf_window_keys(const double *d_vals, uint32_t n, int descending, unsigned long long *d_keys, hipStream_t s);
+// the same keys for group-major values [n][ncol] (ncol <= 32), written as per-column keys [ncol][n] beside the values transposed to
+// [ncol][n]; enqueued on s, no synchronisation
+pvs_status pvs_rrf_window_keys_t(const double *d_vals_t, uint32_t n, uint32_t ncol, int descending, unsigned long long *d_keys, double *d_vals,
+                                 hipStream_t s);
 pvs_status pvs_rrf_sample_keys(const unsigned long long *d_keys, uint32_t n, uint32_t m, unsigned long long *h_out, hipStream_t s);
 // the same for ncol key columns [ncol][n] at once (one round trip each)
 pvs_status pvs_rrf_sample_keys_cols(const unsigned long long *d_keys, uint32_t n, uint32_t ncol, uint32_t m, unsigned long long *h_out, hipStream_t s);

@@ -19,20 +19,44 @@ __device__ inline unsigned long long f64_key(double d) {
 __host__ __device__ inline unsigned long long i64_key(int64_t v) { return (unsigned long long)v ^ 0x8000000000000000ull; }
 
 // window order of one branch: ascending = NULL first, descending = NULL last (SQLite's default NULL placement)
+__device__ inline unsigned long long window_key(double v, int descending) {
+    unsigned long long k;
+    if (v != v)
+        k = descending ? ~0ull : 0ull;
+    else
+        k = descending ? ~f64_key(v) : f64_key(v);
+    // keep real values away from the two NULL codes
+    if (v == v && k == 0ull) k = 1ull;
+    if (v == v && k == ~0ull) k = ~0ull - 1;
+    return k;
+}
 __global__ void k_rank_keys(const double *vals, uint32_t n, int descending, unsigned long long *keys, uint32_t *idx) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const double v = vals[i];
-        unsigned long long k;
-        if (v != v)
-            k = descending ? ~0ull : 0ull;
-        else
-            k = descending ? ~f64_key(v) : f64_key(v);
-        // keep real values away from the two NULL codes
-        if (v == v && k == 0ull) k = 1ull;
-        if (v == v && k == ~0ull) k = ~0ull - 1;
-        keys[i] = k;
+        keys[i] = window_key(vals[i], descending);
         idx[i] = i;
     }
+}
+// Window keys of a batch (pvs_rrf_search_batch): group-major aggregates [n][ncol] (the fused per-item scorer's layout) -> per-query
+// columns keys[ncol][n] and vals[ncol][n].  A workgroup moves 64 groups: it reads their 64 x ncol values as one contiguous run,
+// transposes them in LDS, and each wave writes whole 512-byte column pieces.
+constexpr uint32_t WKT_GROUPS = 64, WKT_MAX_COLS = 32;
+__global__ __launch_bounds__(256) void k_window_keys_t(const double *vals_t, uint32_t n, uint32_t ncol, int descending, unsigned long long *keys,
+                                                      double *vals) {
+    __shared__ double t[WKT_MAX_COLS][WKT_GROUPS + 1];
+    const uint32_t g0 = blockIdx.x * WKT_GROUPS, ng = min(WKT_GROUPS, n - g0), tid = threadIdx.x;
+    const double *src = vals_t + (size_t)g0 * ncol;
+    for (uint32_t i = tid; i < ng * ncol; i += 256) {
+        const uint32_t g = i / ncol;
+        t[i - g * ncol][g] = src[i];
+    }
+    __syncthreads();
+    const uint32_t lane = tid & 63;
+    if (lane < ng)
+        for (uint32_t c = tid >> 6; c < ncol; c += 4) {
+            const double v = t[c][lane];
+            keys[(size_t)c * n + g0 + lane] = window_key(v, descending);
+            vals[(size_t)c * n + g0 + lane] = v;
+        }
 }
 constexpr int RANK_BITS = 40;
 // entry of group slot s of branch b: key = group id, payload = (branch, rank)
@@ -236,6 +260,14 @@ pvs_status pvs_rrf_window_keys(const double *d_vals, uint32_t n, int descending,
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     pvs_scratch_free_on(idx, s);
     if (e != hipSuccess) return pvs_fail(PVS_ERR_DEVICE, "window keys: %s", hipGetErrorString(e));
+    return PVS_OK;
+}
+pvs_status pvs_rrf_window_keys_t(const double *d_vals_t, uint32_t n, uint32_t ncol, int descending, unsigned long long *d_keys, double *d_vals,
+                                 hipStream_t s) {
+    if (n == 0 || ncol == 0) return PVS_OK;
+    if (ncol > WKT_MAX_COLS) return pvs_fail(PVS_ERR_INVALID_ARG, "window keys: at most %u columns per launch", WKT_MAX_COLS);
+    hipLaunchKernelGGL(k_window_keys_t, dim3((n + WKT_GROUPS - 1) / WKT_GROUPS), dim3(256), 0, s, d_vals_t, n, ncol, descending, d_keys, d_vals);
+    HIP_TRY(hipGetLastError());
     return PVS_OK;
 }
 pvs_status pvs_rrf_sample_keys(const unsigned long long *d_keys, uint32_t n, uint32_t m, unsigned long long *h_out, hipStream_t s) {

@@ -99,7 +99,7 @@ __device__ inline uint32_t pow2_at_least(uint32_t n) {
     return p;
 }
 
-__global__ __launch_bounds__(1024) void k_rd_threshold(RdArgs a) {
+__device__ __forceinline__ void rd_threshold(const RdArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t rd_smem[];
     unsigned long long *s = (unsigned long long *)rd_smem;  // [RD_M]
     __shared__ uint32_t hist[256], misc[4];
@@ -117,7 +117,7 @@ __global__ __launch_bounds__(1024) void k_rd_threshold(RdArgs a) {
     if (tid == 0) *b.thr = t;
 }
 // every file with key <= T_b: its slot, in any order (hits collected per workgroup in LDS, one global atomic per workgroup)
-__global__ __launch_bounds__(256) void k_rd_compact(RdBranch b) {
+__device__ __forceinline__ void rd_compact(const RdBranch &b) {
     constexpr uint32_t LIST = 1024;
     __shared__ uint32_t s_n, s_base, s_list[LIST];
     if (threadIdx.x == 0) s_n = 0;
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void k_rd_compact(RdBranch b) {
 }
 // the sampled threshold is a noisy order statistic: cut the list back to the files at or below its own target-th smallest key —
 // still "every file with key <= T'", only with a smaller T' (rrf_bounded does the same with nth_element)
-__global__ __launch_bounds__(1024) void k_rd_cut(RdArgs a) {
+__device__ __forceinline__ void rd_cut(const RdArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t rd_smem[];
     unsigned long long *s = (unsigned long long *)rd_smem;  // [RD_CUT]
     __shared__ uint32_t hist[256], misc[4], s_n;
@@ -182,7 +182,7 @@ __global__ __launch_bounds__(1024) void k_rd_cut(RdArgs a) {
     }
 }
 // candidates = sorted union of the pages
-__global__ __launch_bounds__(1024) void k_rd_union(RdArgs a) {
+__device__ __forceinline__ void rd_union(const RdArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t rd_smem[];
     int64_t *s = (int64_t *)rd_smem;               // [RD_CAND]
     uint32_t *head = (uint32_t *)(s + RD_CAND);    // [RD_CAND] 1 where a new id starts -> its output position
@@ -245,7 +245,7 @@ __global__ __launch_bounds__(1024) void k_rd_union(RdArgs a) {
     }
 }
 // candidate file ids -> their slot in this branch (files are stored in id order) and window key; absent: slot = ~0
-__global__ __launch_bounds__(256) void k_rd_lookup(RdArgs a) {
+__device__ __forceinline__ void rd_lookup(const RdArgs &a) {
     const RdBranch &b = a.br[blockIdx.y];
     const uint32_t c = blockIdx.x * 256 + threadIdx.x, m = *a.m;
     if (c >= m) return;
@@ -262,7 +262,7 @@ __global__ __launch_bounds__(256) void k_rd_lookup(RdArgs a) {
     b.rank[c] = -1;
 }
 // the candidates present in the branch in window order: (key, file id) ascending
-__global__ __launch_bounds__(1024) void k_rd_order(RdArgs a) {
+__device__ __forceinline__ void rd_order(const RdArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t rd_smem[];
     unsigned long long *sk = (unsigned long long *)rd_smem;  // [RD_CAND]
     int64_t *sg = (int64_t *)(sk + RD_CAND);                 // [RD_CAND]
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(1024) void k_rd_order(RdArgs a) {
 }
 // hist[p]++ with p = number of present candidates whose (key, file id) is <= the file's: one pass over the branch's keys, binary
 // search in LDS; files behind every candidate — nearly all of them — are dismissed by one compare and never read their id
-__global__ __launch_bounds__(1024) void k_rd_count(RdBranch b) {  // (80 KB of candidates per workgroup: one workgroup of 16 waves per CU)
+__device__ __forceinline__ void rd_count(const RdBranch &b) {  // (80 KB of candidates per workgroup: one workgroup of 16 waves per CU)
     extern __shared__ __attribute__((aligned(16))) uint8_t rd_smem[];
     const uint32_t m = *b.mp;
     unsigned long long *sk = (unsigned long long *)rd_smem;  // [m]
@@ -333,7 +333,7 @@ __global__ __launch_bounds__(1024) void k_rd_count(RdBranch b) {  // (80 KB of c
         if (sh[i]) atomicAdd(&b.hist[i], (unsigned long long)sh[i]);
 }
 // files strictly before candidate j of the window order = sum_{p <= j} hist[p]; its rank = that + 1
-__global__ __launch_bounds__(1024) void k_rd_ranks(RdArgs a) {
+__device__ __forceinline__ void rd_ranks(const RdArgs &a) {
     __shared__ unsigned long long s_wave[16];
     const RdBranch &b = a.br[blockIdx.x];
     const uint32_t tid = threadIdx.x, mp = *b.mp;
@@ -370,7 +370,7 @@ __device__ inline double rd_term(int32_t k, int64_t rank, double w) {
     const double denom = __builtin_add_overflow((int64_t)k, rank, &di) ? (double)k + (double)rank : (double)di;
     return (1.0 / denom) * w;
 }
-__global__ __launch_bounds__(1024) void k_rd_fuse(RdArgs a) {
+__device__ __forceinline__ void rd_fuse(const RdArgs &a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t rd_smem[];
     unsigned long long *sk = (unsigned long long *)rd_smem;  // [RD_CAND] ~(sortable score): ascending = score descending
     int64_t *sg = (int64_t *)(sk + RD_CAND);                 // [RD_CAND]
@@ -409,6 +409,27 @@ __global__ __launch_bounds__(1024) void k_rd_fuse(RdArgs a) {
     if (tid == 0) *a.out_n = nout;
 }
 
+// The kernels: one round of one query (RdArgs by value), and the same steps for a chunk of queries of a batch (pvs_rrf_search_batch):
+// per-query RdArgs in device memory, the query in blockIdx.y (k_rd_lookup: blockIdx.z; k_rd_compact / k_rd_count: blockIdx.z = branch)
+__global__ __launch_bounds__(1024) void k_rd_threshold(RdArgs a) { rd_threshold(a); }
+__global__ __launch_bounds__(1024) void k_rd_threshold_q(const RdArgs *__restrict__ qa) { rd_threshold(qa[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_rd_cut(RdArgs a) { rd_cut(a); }
+__global__ __launch_bounds__(1024) void k_rd_cut_q(const RdArgs *__restrict__ qa) { rd_cut(qa[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_rd_union(RdArgs a) { rd_union(a); }
+__global__ __launch_bounds__(1024) void k_rd_union_q(const RdArgs *__restrict__ qa) { rd_union(qa[blockIdx.y]); }
+__global__ __launch_bounds__(256) void k_rd_lookup(RdArgs a) { rd_lookup(a); }
+__global__ __launch_bounds__(256) void k_rd_lookup_q(const RdArgs *__restrict__ qa) { rd_lookup(qa[blockIdx.z]); }
+__global__ __launch_bounds__(1024) void k_rd_order(RdArgs a) { rd_order(a); }
+__global__ __launch_bounds__(1024) void k_rd_order_q(const RdArgs *__restrict__ qa) { rd_order(qa[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_rd_ranks(RdArgs a) { rd_ranks(a); }
+__global__ __launch_bounds__(1024) void k_rd_ranks_q(const RdArgs *__restrict__ qa) { rd_ranks(qa[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_rd_fuse(RdArgs a) { rd_fuse(a); }
+__global__ __launch_bounds__(1024) void k_rd_fuse_q(const RdArgs *__restrict__ qa) { rd_fuse(qa[blockIdx.y]); }
+__global__ __launch_bounds__(256) void k_rd_compact(RdBranch b) { rd_compact(b); }
+__global__ __launch_bounds__(256) void k_rd_compact_q(const RdArgs *__restrict__ qa) { rd_compact(qa[blockIdx.y].br[blockIdx.z]); }
+__global__ __launch_bounds__(1024) void k_rd_count(RdBranch b) { rd_count(b); }
+__global__ __launch_bounds__(1024) void k_rd_count_q(const RdArgs *__restrict__ qa) { rd_count(qa[blockIdx.y].br[blockIdx.z]); }
+
 size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
 std::atomic<bool> g_rd_configured{false};
 }  // namespace
@@ -422,10 +443,7 @@ size_t pvs_rrf_round_device_work_bytes(uint32_t nb) {
 }
 size_t pvs_rrf_round_device_out_bytes(uint32_t nb, uint32_t k) { return 64 + al((size_t)nb * 4) + al((size_t)k * 8) * 2 + 256; }
 
-// One round on stream s (which already waits for the branches' window keys).  h_out: a pinned, device-mapped block of
-// pvs_rrf_round_device_out_bytes; the caller synchronises s and reads it with pvs_rrf_round_device_result.
-hipError_t pvs_rrf_round_device(const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb, const PvsRrfParams &p,
-                                uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s) {
+static hipError_t rd_configure() {
     if (!g_rd_configured.load(std::memory_order_acquire)) {
         hipError_t e = hipFuncSetAttribute((const void *)k_rd_threshold, hipFuncAttributeMaxDynamicSharedMemorySize, RD_M * 8);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_cut, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CUT * 8);
@@ -433,9 +451,23 @@ hipError_t pvs_rrf_round_device(const unsigned long long *const *d_keys, const i
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_order, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 20);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_count, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 20 + 16);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_fuse, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 24);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_threshold_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_M * 8);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_cut_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CUT * 8);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_union_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 12);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_order_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 20);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_count_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 20 + 16);
+        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_fuse_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 24);
         if (e != hipSuccess) return e;
         g_rd_configured.store(true, std::memory_order_release);
     }
+    return hipSuccess;
+}
+
+// One round on stream s (which already waits for the branches' window keys).  h_out: a pinned, device-mapped block of
+// pvs_rrf_round_device_out_bytes; the caller synchronises s and reads it with pvs_rrf_round_device_result.
+hipError_t pvs_rrf_round_device(const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb, const PvsRrfParams &p,
+                                uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s) {
+    if (hipError_t e = rd_configure(); e != hipSuccess) return e;
     RdArgs a;
     memset(&a, 0, sizeof a);
     a.nb = nb;
@@ -499,6 +531,91 @@ hipError_t pvs_rrf_round_device(const unsigned long long *const *d_keys, const i
         }
     hipLaunchKernelGGL(k_rd_ranks, dim3(nb), dim3(RD_T), 0, s, a);
     hipLaunchKernelGGL(k_rd_fuse, dim3(1), dim3(RD_T), RD_CAND * 24, s, a);
+    return hipGetLastError();
+}
+
+// pvs_rrf_search_batch: one round for each of nq queries, every step ONE launch for the whole chunk, one synchronisation for all
+// (the caller's).  d_keys[q * nb + b]: query q's window keys in branch b (the branch's file ids and count are shared).  Query q's
+// output lands at h_out + q * pvs_rrf_round_device_out_stride(nb, k), read with pvs_rrf_round_device_result.
+size_t pvs_rrf_round_device_out_stride(uint32_t nb, uint32_t k) { return al(pvs_rrf_round_device_out_bytes(nb, k)); }
+size_t pvs_rrf_round_device_batch_work_bytes(uint32_t nb, uint32_t nq) {
+    return al((size_t)nq * nb * 4) + (size_t)nq * al(pvs_rrf_round_device_work_bytes(nb)) + al((size_t)nq * sizeof(RdArgs));
+}
+size_t pvs_rrf_round_device_batch_out_bytes(uint32_t nb, uint32_t k, uint32_t nq) {
+    return (size_t)nq * pvs_rrf_round_device_out_stride(nb, k) + al((size_t)nq * sizeof(RdArgs));
+}
+hipError_t pvs_rrf_round_device_batch(uint32_t nq, const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb,
+                                      const PvsRrfParams &p, uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s) {
+    if (nq == 0) return hipSuccess;
+    if (hipError_t e = rd_configure(); e != hipSuccess) return e;
+    uint8_t *w = (uint8_t *)d_work;
+    uint32_t *cnt = (uint32_t *)w;  // every (query, branch) page counter side by side: one fill
+    w += al((size_t)nq * nb * 4);
+    const size_t ostride = pvs_rrf_round_device_out_stride(nb, k);
+    RdArgs *h_args = (RdArgs *)(h_out + (size_t)nq * ostride);  // staged in the pinned block, copied to the device below
+    for (uint32_t q = 0; q < nq; q++) {
+        RdArgs &a = h_args[q];
+        memset(&a, 0, sizeof a);
+        a.nb = nb;
+        a.target = target;
+        a.k = k;
+        a.p = p;
+        uint8_t *wq = w + (size_t)q * al(pvs_rrf_round_device_work_bytes(nb));
+        auto take = [&](size_t bytes) {
+            uint8_t *r = wq;
+            wq += al(bytes);
+            return r;
+        };
+        for (uint32_t b = 0; b < nb; b++) {
+            RdBranch &r = a.br[b];
+            r.keys = d_keys[(size_t)q * nb + b];
+            r.gids = d_gids[b];
+            r.n = n[b];
+            r.thr = (unsigned long long *)take(8);
+            (void)take(4);
+            r.cnt = cnt + (size_t)q * nb + b;
+            r.slots = (uint32_t *)take(RD_CUT * 4);
+            r.page_g = (int64_t *)take(RD_PAGE * 8);
+            r.cslot = (uint32_t *)take(RD_CAND * 4);
+            r.ckey = (unsigned long long *)take(RD_CAND * 8);
+            r.ok = (unsigned long long *)take(RD_CAND * 8);
+            r.og = (int64_t *)take(RD_CAND * 8);
+            r.oi = (uint32_t *)take(RD_CAND * 4);
+            r.mp = (uint32_t *)take(4);
+            r.hist = (unsigned long long *)take((RD_CAND + 1) * 8);
+            r.rank = (int64_t *)take(RD_CAND * 8);
+        }
+        a.cand = (int64_t *)take(RD_CAND * 8);
+        a.m = (uint32_t *)take(4);
+        uint8_t *o = h_out + (size_t)q * ostride;
+        a.flags = (uint32_t *)o;
+        a.out_m = (uint32_t *)(o + 16);
+        a.out_n = (uint32_t *)(o + 32);
+        a.R = (uint32_t *)(o + 64);
+        a.out_g = (int64_t *)(o + 64 + al((size_t)nb * 4));
+        a.out_s = (double *)((uint8_t *)a.out_g + al((size_t)k * 8));
+        *(volatile uint32_t *)a.flags = 0;
+        *(volatile uint32_t *)a.out_m = 0;
+        *(volatile uint32_t *)a.out_n = 0;
+    }
+    RdArgs *d_args = (RdArgs *)(w + (size_t)nq * al(pvs_rrf_round_device_work_bytes(nb)));
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nq * nb * 4, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_args, h_args, (size_t)nq * sizeof(RdArgs), hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return e;
+    unsigned gc = 1, gn = 1;  // (the longest branch's grid; the passes are grid-stride, a shorter branch's extra workgroups find nothing)
+    for (uint32_t b = 0; b < nb; b++) {
+        gc = std::max<unsigned>(gc, (unsigned)std::min<uint64_t>(((uint64_t)n[b] + 255) / 256, 2048));
+        gn = std::max<unsigned>(gn, (unsigned)std::min<uint64_t>(((uint64_t)n[b] + RD_T - 1) / RD_T, 256));
+    }
+    hipLaunchKernelGGL(k_rd_threshold_q, dim3(nb, nq), dim3(RD_T), RD_M * 8, s, d_args);
+    hipLaunchKernelGGL(k_rd_compact_q, dim3(gc, nq, nb), dim3(256), 0, s, d_args);
+    hipLaunchKernelGGL(k_rd_cut_q, dim3(nb, nq), dim3(RD_T), RD_CUT * 8, s, d_args);
+    hipLaunchKernelGGL(k_rd_union_q, dim3(1, nq), dim3(RD_T), RD_CAND * 12, s, d_args);
+    hipLaunchKernelGGL(k_rd_lookup_q, dim3(RD_CAND / 256, nb, nq), dim3(256), 0, s, d_args);
+    hipLaunchKernelGGL(k_rd_order_q, dim3(nb, nq), dim3(RD_T), RD_CAND * 20, s, d_args);
+    hipLaunchKernelGGL(k_rd_count_q, dim3(gn, nq, nb), dim3(RD_T), RD_CAND * 20 + 16, s, d_args);
+    hipLaunchKernelGGL(k_rd_ranks_q, dim3(nb, nq), dim3(RD_T), 0, s, d_args);
+    hipLaunchKernelGGL(k_rd_fuse_q, dim3(1, nq), dim3(RD_T), RD_CAND * 24, s, d_args);
     return hipGetLastError();
 }
 // after the stream drained: flags != 0 -> the round must be redone by the host form

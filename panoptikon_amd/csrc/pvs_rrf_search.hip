@@ -5,7 +5,7 @@
 #include <string>
 #include <thread>
 
-#include "pvs_index.hpp"
+#include "pvs_rrf_search.hpp"
 
 static thread_local int32_t g_rrf_last_path = 0;
 PVS_EXPORT int32_t pvs_rrf_last_path(void) { return g_rrf_last_path; }
@@ -37,17 +37,6 @@ PVS_EXPORT pvs_status pvs_debug_rrf_digests(uint64_t *out, uint32_t *out_branche
     *out_path = g_rrf_dig.path;
     return PVS_OK;
 }
-
-// One branch of an OR-composition, scored (pvs_rrf_cols in the C ABI): every group's aggregate (f64, the reference's
-// arithmetic) and its window key.
-struct pvs_rrf_cols {
-    pvs_index *ix = nullptr;
-    double *d_vals = nullptr;               // [n_groups]
-    unsigned long long *d_keys = nullptr;   // [n_groups] order-preserving window key (NULL placement and direction folded in)
-    uint32_t n_groups = 0;
-    std::vector<unsigned long long> sample;  // sorted sample of the keys (threshold proposals)
-};
-typedef pvs_rrf_cols RrfBranchCols;
 
 // every row's exact distance (the dist_{cte} column), aggregated per group in row order
 static pvs_status rrf_score_branch(const pvs_rrf_branch &b, RrfBranchCols *out, uint64_t *dig = nullptr) {
@@ -215,35 +204,6 @@ static double rrf_score_host(const int64_t *ranks, const PvsRrfParams &p) {
 //      quarter of a branch falls back to the full ranking below.
 // Cost beside the exact scoring of every row: a few passes over 8 B per group instead of three multi-pass radix sorts of
 // all groups (configs[4]: 2 x 8.3M groups — the sorts were 10 of 16 ms).
-// The branches of a composition live in different indexes (their own streams, contexts and scratch): their per-branch steps run
-// on one host thread each, so that the round trips of one branch (uploads, the exact-range flag, page and count read-backs)
-// hide behind the other's kernels.  Branches that share an index run one after the other.
-template <class F>
-static pvs_status per_branch(const pvs_rrf_branch *br, uint32_t nb, F &&f) {
-    bool distinct = true;
-    for (uint32_t a = 0; a < nb; a++)
-        for (uint32_t b = a + 1; b < nb; b++) distinct &= br[a].idx != br[b].idx;
-    const bool serial = pvs_dbg(PVS_DBG_RRF_SERIAL) != 0;  // tuning
-    if (nb == 1 || !distinct || serial) {
-        for (uint32_t b = 0; b < nb; b++) PVS_TRY(f(b));
-        return PVS_OK;
-    }
-    std::vector<pvs_status> st(nb, PVS_OK);
-    std::vector<std::string> msg(nb);
-    std::vector<std::thread> th;
-    for (uint32_t b = 1; b < nb; b++)
-        th.emplace_back([&, b] {
-            st[b] = f(b);
-            if (st[b] != PVS_OK) msg[b] = pvs_last_error();
-        });
-    st[0] = f(0);
-    for (auto &t : th) t.join();
-    if (st[0] != PVS_OK) return st[0];
-    for (uint32_t b = 1; b < nb; b++)
-        if (st[b] != PVS_OK) return pvs_fail(st[b], "%s", msg[b].c_str());
-    return PVS_OK;
-}
-
 // pvs_debug_set("rrf_trace", 1): host wall time of every phase of a composed query on stderr (tuning)
 struct RrfTrace {
     bool on = pvs_dbg(PVS_DBG_RRF_TRACE) != 0;
@@ -315,27 +275,49 @@ static pvs_status rrf_round_on_device(const pvs_rrf_branch *br, std::vector<RrfB
     return st;
 }
 
-static pvs_status rrf_bounded(const pvs_rrf_branch *br, std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k,
-                              int64_t *out_groups, double *out_scores, uint32_t *out_count, bool *done, RrfDigestRec *dig = nullptr) {
-    *done = false;
-    const uint32_t nb = p.n_branches;
+// The bounded fusion applies at all (non-negative terms, enough groups): the first page size, else 0
+static uint64_t rrf_bounded_target(const std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k) {
     uint64_t total_groups = 0;
-    for (uint32_t b = 0; b < nb; b++) {
-        if (!(p.w[b] >= 0.0) || p.k[b] < 0) return PVS_OK;  // the bound needs non-negative terms (NaN weights too: full path)
+    for (uint32_t b = 0; b < p.n_branches; b++) {
+        if (!(p.w[b] >= 0.0) || p.k[b] < 0) return 0;  // the bound needs non-negative terms (NaN weights too: full path)
         total_groups += cols[b].n_groups;
     }
-    if (total_groups < 65536) return PVS_OK;  // small: the full ranking is cheap
+    if (total_groups < 65536) return 0;  // small: the full ranking is cheap
     // first page size: R_b ~ 4k already puts the bound (sum of w/(k_b + R_b + 1)) far below the k-th fused score unless the
     // branches barely overlap near the top; every host-side step below is linear (or n log n) in the pages
-    uint64_t target = std::max<uint64_t>(4ull * k, 1024);
+    return std::max<uint64_t>(4ull * k, 1024);
+}
+// a page of this target would hold a quarter of some branch: the full ranking instead
+static bool rrf_page_too_large(const std::vector<RrfBranchCols> &cols, uint32_t nb, uint64_t target) {
+    for (uint32_t b = 0; b < nb; b++)
+        if (cols[b].n_groups && target * 4 >= cols[b].n_groups) return true;
+    return false;
+}
+uint64_t rrf_device_round_target(const std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k) {
+    const uint64_t target = rrf_bounded_target(cols, p, k);
+    if (!target || pvs_dbg(PVS_DBG_RRF_FULL) || pvs_dbg(PVS_DBG_RRF_HOST_ROUNDS) || rrf_page_too_large(cols, p.n_branches, target) ||
+        !pvs_rrf_round_device_supported(p.n_branches, target, k))
+        return 0;
+    return target;
+}
+
+// first_round > 0 / device_round = false: the caller already ran round 0 on the device (pvs_rrf_search_batch) — the bound was not met
+// (continue at round 1), or a size limit was hit (round 0 again, in host form)
+static pvs_status rrf_bounded(const pvs_rrf_branch *br, std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k,
+                              int64_t *out_groups, double *out_scores, uint32_t *out_count, bool *done, RrfDigestRec *dig = nullptr,
+                              int first_round = 0, bool device_round = true) {
+    *done = false;
+    const uint32_t nb = p.n_branches;
+    uint64_t target = rrf_bounded_target(cols, p, k);
+    if (!target) return PVS_OK;
+    for (int r = 0; r < first_round; r++) target *= 4;
     RrfTrace tr;
-    for (int round = 0; round < 6; round++, target *= 4) {
+    for (int round = first_round; round < 6; round++, target *= 4) {
         std::vector<uint32_t> R(nb, 0);
         std::vector<int64_t> cand;
-        for (uint32_t b = 0; b < nb; b++)
-            if (cols[b].n_groups && target * 4 >= cols[b].n_groups) return PVS_OK;  // a page that would hold a quarter of the branch: full ranking
+        if (rrf_page_too_large(cols, nb, target)) return PVS_OK;  // a page that would hold a quarter of the branch: full ranking
         // the first round entirely on the device (the stage digests read the host form's intermediate results: that form then)
-        if (round == 0 && !dig && !pvs_dbg(PVS_DBG_RRF_HOST_ROUNDS) && pvs_rrf_round_device_supported(nb, target, k)) {
+        if (round == 0 && device_round && !dig && !pvs_dbg(PVS_DBG_RRF_HOST_ROUNDS) && pvs_rrf_round_device_supported(nb, target, k)) {
             bool usable = false;
             uint32_t m = 0;
             PVS_TRY(rrf_round_on_device(br, cols, p, target, k, out_groups, out_scores, out_count, &usable, done, &m));
@@ -444,19 +426,23 @@ static pvs_status rrf_bounded(const pvs_rrf_branch *br, std::vector<RrfBranchCol
 
 static pvs_status rrf_search_impl(const pvs_rrf_branch *br, uint32_t nb, uint32_t k, int64_t *out_groups, double *out_scores, uint32_t *out_count);
 
+void rrf_set_last_path(int32_t path) { g_rrf_last_path = path; }
+
+bool rrf_branches_keyed(const pvs_rrf_branch *br, uint32_t nb) {
+    bool keyed = false;
+    if (br && nb >= 1 && nb <= (uint32_t)PVS_RRF_MAX_BRANCHES)
+        for (uint32_t b = 0; b < nb; b++) keyed |= br[b].idx && br[b].idx->order_rows == br[b].idx->n && br[b].idx->n;
+    return keyed;
+}
+
 // The fused page under the reference's final ordering (`ORDER BY order_rank DESC ..., last_modified DESC`, pql/model.rs:547-553)
 // when the branches' rows carry order keys (pvs_index_set_order_keys): groups that tie on the fused score — two files that swap
 // places between two branches already do — come out by key descending, then group id.  The page is taken far enough past k
 // that every group tying with the k-th score is on it (or the page is everything), re-ordered on the host and cut to k.  A
 // group's key: from the first branch (in branch order) that carries keys and holds the group.
-PVS_EXPORT pvs_status pvs_rrf_search(const pvs_rrf_branch *br, uint32_t nb, uint32_t k, int64_t *out_groups, double *out_scores,
-                                     uint32_t *out_count) {
-    const uint32_t nb_ok = br && nb <= (uint32_t)PVS_RRF_MAX_BRANCHES ? nb : 0;
-    GateSharedMany gate(br, br + nb_ok, [](const pvs_rrf_branch &b) { return b.idx; });  // (pvs_gate.hip: every branch's index, in address order)
-    bool keyed = false;
-    if (br && nb >= 1 && nb <= (uint32_t)PVS_RRF_MAX_BRANCHES)
-        for (uint32_t b = 0; b < nb; b++) keyed |= br[b].idx && br[b].idx->order_rows == br[b].idx->n && br[b].idx->n;
-    if (!keyed) return rrf_search_impl(br, nb, k, out_groups, out_scores, out_count);
+pvs_status rrf_keyed_page(const pvs_rrf_branch *br, uint32_t nb, uint32_t k,
+                          const std::function<pvs_status(uint32_t kk, int64_t *g, double *sc, uint32_t *cnt)> &page, int64_t *out_groups,
+                          double *out_scores, uint32_t *out_count) {
     if (!out_groups || !out_scores || !out_count) return pvs_fail(PVS_ERR_INVALID_ARG, "null argument");
     if (k < 1) return pvs_fail(PVS_ERR_INVALID_ARG, "k must be a positive integer");
     std::vector<int64_t> g;
@@ -466,7 +452,7 @@ PVS_EXPORT pvs_status pvs_rrf_search(const pvs_rrf_branch *br, uint32_t nb, uint
         kk = std::min<uint64_t>(kk, 0x7fffffffu);
         g.resize(kk);
         sc.resize(kk);
-        PVS_TRY(rrf_search_impl(br, nb, (uint32_t)kk, g.data(), sc.data(), &cnt));
+        PVS_TRY(page((uint32_t)kk, g.data(), sc.data(), &cnt));
         if (cnt < kk || cnt <= k || sc[cnt - 1] < sc[k - 1] || kk == 0x7fffffffu) break;  // (scores are never NaN: sums of finite terms)
     }
     struct E {
@@ -494,15 +480,22 @@ PVS_EXPORT pvs_status pvs_rrf_search(const pvs_rrf_branch *br, uint32_t nb, uint
     return PVS_OK;
 }
 
-static pvs_status rrf_search_impl(const pvs_rrf_branch *br, uint32_t nb, uint32_t k, int64_t *out_groups, double *out_scores,
-                                  uint32_t *out_count) {
-    if (!br || !out_groups || !out_scores || !out_count) return pvs_fail(PVS_ERR_INVALID_ARG, "null argument");
-    if (nb < 1 || nb > (uint32_t)PVS_RRF_MAX_BRANCHES) return pvs_fail(PVS_ERR_INVALID_ARG, "1..%d branches", PVS_RRF_MAX_BRANCHES);
-    if (k < 1) return pvs_fail(PVS_ERR_INVALID_ARG, "k must be a positive integer");
-    PvsRrfParams p;
-    memset(&p, 0, sizeof p);
-    p.n_branches = nb;
-    uint64_t total = 0;
+pvs_status rrf_search_one(const pvs_rrf_branch *br, uint32_t nb, uint32_t k, int64_t *out_groups, double *out_scores, uint32_t *out_count) {
+    if (!rrf_branches_keyed(br, nb)) return rrf_search_impl(br, nb, k, out_groups, out_scores, out_count);
+    return rrf_keyed_page(
+        br, nb, k, [&](uint32_t kk, int64_t *g, double *sc, uint32_t *cnt) { return rrf_search_impl(br, nb, kk, g, sc, cnt); }, out_groups, out_scores,
+        out_count);
+}
+
+PVS_EXPORT pvs_status pvs_rrf_search(const pvs_rrf_branch *br, uint32_t nb, uint32_t k, int64_t *out_groups, double *out_scores,
+                                     uint32_t *out_count) {
+    const uint32_t nb_ok = br && nb <= (uint32_t)PVS_RRF_MAX_BRANCHES ? nb : 0;
+    GateSharedMany gate(br, br + nb_ok, [](const pvs_rrf_branch &b) { return b.idx; });  // (pvs_gate.hip: every branch's index, in address order)
+    return rrf_search_one(br, nb, k, out_groups, out_scores, out_count);
+}
+
+pvs_status rrf_check_multi(const pvs_rrf_branch *br, uint32_t nb, bool *multi) {
+    *multi = false;
     for (uint32_t b = 0; b < nb; b++)
         if (br[b].idx && is_multi(br[b].idx)) {
             if (!br[0].idx || !is_multi(br[0].idx)) return pvs_fail(PVS_ERR_INVALID_ARG, "pvs_rrf_search: single- and multi-device branches cannot be mixed");
@@ -511,53 +504,52 @@ static pvs_status rrf_search_impl(const pvs_rrf_branch *br, uint32_t nb, uint32_
                 if (br[j].agg != PVS_AGG_MIN && br[j].agg != PVS_AGG_MAX && br[j].agg != PVS_AGG_AVG && !br[j].row_weights)
                     return pvs_fail(PVS_ERR_INVALID_ARG, "aggregation must be MIN, MAX or AVG");
             }
-            return multi_rrf_search(br, nb, k, out_groups, out_scores, out_count);
+            *multi = true;
+            return PVS_OK;
         }
+    return PVS_OK;
+}
+
+pvs_status rrf_check_branches(const pvs_rrf_branch *br, uint32_t nb, PvsRrfParams *p) {
+    memset(p, 0, sizeof *p);
+    p->n_branches = nb;
     for (uint32_t b = 0; b < nb; b++) {
         pvs_index *ix = br[b].idx;
         PVS_TRY(validate_search(ix, br[b].query, br[b].query_dtype, 1, 1, br[b].metric));
         if (ix->device != br[0].idx->device) return pvs_fail(PVS_ERR_INVALID_ARG, "all branches must live on one device");
         if (!br[b].row_weights && br[b].agg != PVS_AGG_MIN && br[b].agg != PVS_AGG_MAX && br[b].agg != PVS_AGG_AVG)
             return pvs_fail(PVS_ERR_INVALID_ARG, "aggregation must be MIN, MAX or AVG");
-        p.k[b] = br[b].rrf_k;
-        p.w[b] = br[b].weight;
+        p->k[b] = br[b].rrf_k;
+        p->w[b] = br[b].weight;
         HIP_TRY(hipSetDevice(ix->device));
         std::lock_guard<std::mutex> lk(ix->mu);
         PVS_TRY(ensure_groups(ix));
-        total += ix->n_groups;
     }
-    std::vector<RrfBranchCols> cols(nb);
+    return PVS_OK;
+}
+
+static pvs_status rrf_fuse_impl(const pvs_rrf_branch *br, std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k, int64_t *out_groups,
+                                double *out_scores, uint32_t *out_count, int *path, RrfDigestRec *dig, int first_round = 0, bool device_round = true) {
+    const uint32_t nb = p.n_branches;
+    const bool force_full = pvs_dbg(PVS_DBG_RRF_FULL) != 0;  // tests and profiles: compare the two paths
+    if (!force_full) {
+        bool done = false;
+        PVS_TRY(rrf_bounded(br, cols, p, k, out_groups, out_scores, out_count, &done, dig, first_round, device_round));
+        if (done) {
+            *path = 1;
+            for (uint32_t i = *out_count; i < k; i++) {
+                out_groups[i] = -1;
+                out_scores[i] = __builtin_nan("");
+            }
+            return PVS_OK;
+        }
+    }
+    // full ranking: every group of every branch ranked (stable radix sorts), entries appended in branch order, fused by sort
+    *path = 2;
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < nb; b++) total += cols[b].n_groups;
     unsigned long long *cat_key = nullptr, *cat_pay = nullptr;
     auto body = [&]() -> pvs_status {
-        RrfTrace tr;
-        const bool digest = pvs_dbg(PVS_DBG_RRF_DIGEST) != 0;
-        RrfDigestRec dig;
-        memset(&dig, 0, sizeof dig);
-        dig.nb = nb;
-        auto publish = [&](int path) {
-            if (!digest) return;
-            dig.path = path;
-            std::lock_guard<std::mutex> lk(g_rrf_dig_mu);
-            g_rrf_dig = dig;
-        };
-        PVS_TRY(per_branch(br, nb, [&](uint32_t b) { return rrf_score_branch(br[b], &cols[b], digest ? dig.v[b] : nullptr); }));
-        tr.lap("score branches");
-        const bool force_full = pvs_dbg(PVS_DBG_RRF_FULL) != 0;  // tests and profiles: compare the two paths
-        if (!force_full) {
-            bool done = false;
-            PVS_TRY(rrf_bounded(br, cols, p, k, out_groups, out_scores, out_count, &done, digest ? &dig : nullptr));
-            if (done) {
-                publish(1);
-                g_rrf_last_path = 1;
-                for (uint32_t i = *out_count; i < k; i++) {
-                    out_groups[i] = -1;
-                    out_scores[i] = __builtin_nan("");
-                }
-                return PVS_OK;
-            }
-        }
-        // full ranking: every group of every branch ranked (stable radix sorts), entries appended in branch order, fused by sort
-        g_rrf_last_path = 2;
         HIP_TRY(hipSetDevice(br[0].idx->device));
         HIP_TRY(pvs_malloc_retry((void **)&cat_key, std::max<uint64_t>(total, 1) * 8));
         HIP_TRY(pvs_malloc_retry((void **)&cat_pay, std::max<uint64_t>(total, 1) * 8));
@@ -567,11 +559,54 @@ static pvs_status rrf_search_impl(const pvs_rrf_branch *br, uint32_t nb, uint32_
             if (ix->n == 0) continue;
             PVS_TRY(pvs_rrf_rank_branch(cols[b].d_vals, ix->d_grp_ids, ix->n_groups, br[b].row_n_descending != 0, b, cat_key + off, cat_pay + off,
                                         ix->search_stream));
-            if (digest) PVS_TRY(pvs_digest_device(cat_pay + off, ix->n_groups, 8, &dig.v[b][3], ix->search_stream));
+            if (dig) PVS_TRY(pvs_digest_device(cat_pay + off, ix->n_groups, 8, &dig->v[b][3], ix->search_stream));
             off += ix->n_groups;
         }
-        publish(2);
         return pvs_rrf_fuse_device(cat_key, cat_pay, off, p, k, out_groups, out_scores, out_count, br[0].idx->search_stream);
+    };
+    pvs_status st = body();
+    if (st != PVS_OK) (void)hipDeviceSynchronize();  // (a failure part-way may have left work queued on a branch's stream)
+    hipFree(cat_key);
+    hipFree(cat_pay);
+    return st;
+}
+pvs_status rrf_fuse_scored(const pvs_rrf_branch *br, std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k, int64_t *out_groups,
+                           double *out_scores, uint32_t *out_count, int *path) {
+    return rrf_fuse_impl(br, cols, p, k, out_groups, out_scores, out_count, path, nullptr);
+}
+pvs_status rrf_fuse_continue(const pvs_rrf_branch *br, std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k, int64_t *out_groups,
+                             double *out_scores, uint32_t *out_count, int *path, int first_round, bool device_round) {
+    return rrf_fuse_impl(br, cols, p, k, out_groups, out_scores, out_count, path, nullptr, first_round, device_round);
+}
+
+static pvs_status rrf_search_impl(const pvs_rrf_branch *br, uint32_t nb, uint32_t k, int64_t *out_groups, double *out_scores,
+                                  uint32_t *out_count) {
+    if (!br || !out_groups || !out_scores || !out_count) return pvs_fail(PVS_ERR_INVALID_ARG, "null argument");
+    if (nb < 1 || nb > (uint32_t)PVS_RRF_MAX_BRANCHES) return pvs_fail(PVS_ERR_INVALID_ARG, "1..%d branches", PVS_RRF_MAX_BRANCHES);
+    if (k < 1) return pvs_fail(PVS_ERR_INVALID_ARG, "k must be a positive integer");
+    bool multi = false;
+    PVS_TRY(rrf_check_multi(br, nb, &multi));
+    if (multi) return multi_rrf_search(br, nb, k, out_groups, out_scores, out_count);
+    PvsRrfParams p;
+    PVS_TRY(rrf_check_branches(br, nb, &p));
+    std::vector<RrfBranchCols> cols(nb);
+    auto body = [&]() -> pvs_status {
+        RrfTrace tr;
+        const bool digest = pvs_dbg(PVS_DBG_RRF_DIGEST) != 0;
+        RrfDigestRec dig;
+        memset(&dig, 0, sizeof dig);
+        dig.nb = nb;
+        PVS_TRY(per_branch(br, nb, [&](uint32_t b) { return rrf_score_branch(br[b], &cols[b], digest ? dig.v[b] : nullptr); }));
+        tr.lap("score branches");
+        int path = 0;
+        PVS_TRY(rrf_fuse_impl(br, cols, p, k, out_groups, out_scores, out_count, &path, digest ? &dig : nullptr));
+        g_rrf_last_path = path;
+        if (digest) {
+            dig.path = path;
+            std::lock_guard<std::mutex> lk(g_rrf_dig_mu);
+            g_rrf_dig = dig;
+        }
+        return PVS_OK;
     };
     pvs_status st = body();
     if (st != PVS_OK) (void)hipDeviceSynchronize();  // (a failure part-way may have left work queued on a branch's stream)
@@ -579,7 +614,5 @@ static pvs_status rrf_search_impl(const pvs_rrf_branch *br, uint32_t nb, uint32_
         pvs_scratch_free(c.d_vals);
         pvs_scratch_free(c.d_keys);
     }
-    hipFree(cat_key);
-    hipFree(cat_pay);
     return st;
 }

@@ -173,6 +173,34 @@ def rrf_search(branches, k: int):
     return og[: oc.value], ov[: oc.value]
 
 
+def rrf_search_batch(branches, k: int):
+    """rrf_search for a batch of composed queries (pvs_rrf_search_batch): every branch's `query` is a [batch, dim] array, row j of
+    each together forming composed query j -> (groups[batch, k], scores[batch, k], counts[batch]); row j's first counts[j] slots
+    are rrf_search's page for that query, the rest -1 / NaN."""
+    if not branches:
+        raise ValueError("rrf_search_batch needs at least one branch")
+    sizes = set()
+    for b in branches:
+        q = np.asarray(b["query"])
+        if q.ndim != 2:
+            raise ValueError(f"each branch's query must be a [batch, dim] array, got shape {q.shape}")
+        if q.shape[1] != b["index"].dim:
+            raise ValueError(f"query dimension {q.shape[1]} != index dimension {b['index'].dim}")
+        sizes.add(q.shape[0])
+    if len(sizes) != 1:
+        raise ValueError(f"every branch needs the same number of queries, got {sorted(sizes)}")
+    batch = sizes.pop()
+    arr = (L.RrfBranch * len(branches))()
+    keep = []
+    for i, b in enumerate(branches):
+        arr[i] = _branch_struct(b, keep)
+    og = np.full((batch, k), -1, np.int64)
+    ov = np.full((batch, k), np.nan, np.float64)
+    oc = np.zeros(batch, np.uint32)
+    L.check(L.lib().pvs_rrf_search_batch(C.byref(arr), len(branches), batch, k, _ptr(og), _ptr(ov), _ptr(oc)))
+    return og, ov, oc
+
+
 def merge_group_pages(groups, values, counts, k: int, keys=None):
     """groups/values: [world][batch][k] (i64 / f64); counts: [world][batch] -> merged per-item pages.  keys ([world][batch][k]
     i64, optional): the second sort key of every entry's group (pvs_merge_group_pages_keyed)."""
