@@ -359,19 +359,15 @@ struct PvsRrfParams {
     int32_t k[PVS_RRF_MAX_BRANCHES];
     double w[PVS_RRF_MAX_BRANCHES];
 };
-// one round of the bounded fusion on the device (pvs_rrf_device.hip): everything behind the window keys, one synchronisation
+// one round of the bounded fusion on the device for nq queries (pvs_rrf_device.hip): everything behind the window keys, every step one
+// launch for all queries, one synchronisation.  d_keys[q * nb + b]; work and pinned output blocks of the sizes below; query q's output
+// at h_out + q * pvs_rrf_round_device_out_stride
 bool pvs_rrf_round_device_supported(uint32_t nb, uint64_t target, uint32_t k);
-size_t pvs_rrf_round_device_work_bytes(uint32_t nb);
-size_t pvs_rrf_round_device_out_bytes(uint32_t nb, uint32_t k);
-hipError_t pvs_rrf_round_device(const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb, const PvsRrfParams &p,
-                                uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s);
-// the same round for nq queries of a batch, every step one launch for the chunk: d_keys[q * nb + b]; work and pinned output blocks
-// of the two sizes below; query q's output at h_out + q * pvs_rrf_round_device_out_stride
 size_t pvs_rrf_round_device_out_stride(uint32_t nb, uint32_t k);
-size_t pvs_rrf_round_device_batch_work_bytes(uint32_t nb, uint32_t nq);
-size_t pvs_rrf_round_device_batch_out_bytes(uint32_t nb, uint32_t k, uint32_t nq);
-hipError_t pvs_rrf_round_device_batch(uint32_t nq, const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb,
-                                      const PvsRrfParams &p, uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s);
+size_t pvs_rrf_round_device_work_bytes(uint32_t nb, uint32_t nq);
+size_t pvs_rrf_round_device_out_bytes(uint32_t nb, uint32_t k, uint32_t nq);
+hipError_t pvs_rrf_round_device(uint32_t nq, const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb,
+                                const PvsRrfParams &p, uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s);
 void pvs_rrf_round_device_result(const uint8_t *h_out, uint32_t nb, uint32_t k, uint32_t *flags, uint32_t *R, uint32_t *m, uint32_t *n_out, const int64_t **groups,
                                  const double **scores);
 // order-independent 64-bit digest of n words of 4 or 8 bytes (synchronous; race hunting, pvs_debug_rrf_digests)
@@ -383,13 +379,10 @@ pvs_status pvs_rrf_window_keys(const double *d_vals, uint32_t n, int descending,
 // [ncol][n]; enqueued on s, no synchronisation
 pvs_status pvs_rrf_window_keys_t(const double *d_vals_t, uint32_t n, uint32_t ncol, int descending, unsigned long long *d_keys, double *d_vals,
                                  hipStream_t s);
-pvs_status pvs_rrf_sample_keys(const unsigned long long *d_keys, uint32_t n, uint32_t m, unsigned long long *h_out, hipStream_t s);
-// the same for ncol key columns [ncol][n] at once (one round trip each)
+// m evenly spaced keys of each of ncol key columns [ncol][n] (one round trip)
 pvs_status pvs_rrf_sample_keys_cols(const unsigned long long *d_keys, uint32_t n, uint32_t ncol, uint32_t m, unsigned long long *h_out, hipStream_t s);
 pvs_status pvs_rrf_pages_cols(const unsigned long long *d_keys, const int64_t *d_gids, uint32_t n, uint32_t ncol, const unsigned long long *h_thr,
                               uint32_t cap, int64_t *out_gids, unsigned long long *out_keys, uint32_t *out_count, hipStream_t s);
-pvs_status pvs_rrf_page(const unsigned long long *d_keys, const int64_t *d_gids, uint32_t n, unsigned long long thr, uint32_t cap,
-                        int64_t *out_gids, unsigned long long *out_keys, uint32_t *out_count, hipStream_t s);
 pvs_status pvs_rrf_lookup(const unsigned long long *d_keys, const int64_t *d_gids, uint32_t n, const int64_t *cand, uint32_t m,
                           unsigned long long *out_keys, uint8_t *out_present, hipStream_t s);
 pvs_status pvs_rrf_count_below(const unsigned long long *d_keys, const int64_t *d_gids, uint32_t n, const unsigned long long *ckeys,

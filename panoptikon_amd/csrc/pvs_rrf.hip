@@ -30,10 +30,11 @@ __device__ inline unsigned long long window_key(double v, int descending) {
     if (v == v && k == ~0ull) k = ~0ull - 1;
     return k;
 }
+// window keys of n values; idx (may be null): the identity permutation beside them (the radix sort's payload)
 __global__ void k_rank_keys(const double *vals, uint32_t n, int descending, unsigned long long *keys, uint32_t *idx) {
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         keys[i] = window_key(vals[i], descending);
-        idx[i] = i;
+        if (idx) idx[i] = i;
     }
 }
 // Window keys of a batch (pvs_rrf_search_batch): group-major aggregates [n][ncol] (the fused per-item scorer's layout) -> per-query
@@ -132,44 +133,6 @@ __global__ void k_rrf_emit(const unsigned long long *key2_sorted, const uint32_t
 inline unsigned grid_for(uint64_t n) { return (unsigned)std::min<uint64_t>(std::max<uint64_t>((n + 255) / 256, 1), 65535); }
 
 // ---- bounded fusion (pvs_rrf_search's fast path): pages of each branch's ranking instead of ranking every group
-__global__ void k_sample_keys(const unsigned long long *keys, uint32_t n, uint32_t m, unsigned long long *out) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) out[i] = keys[(uint64_t)i * n / m];
-}
-// every group whose window key is <= thr, in any order: (slot, key)
-// (hits are collected per workgroup in LDS and claim their slots with one global atomic: thousands of hits on one counter
-//  serialise in L2 — see k_page_compact_cols)
-__global__ __launch_bounds__(256) void k_page_compact(const unsigned long long *keys, uint32_t n, unsigned long long thr, uint32_t cap, uint32_t *count,
-                                                      uint32_t *slots) {
-    constexpr uint32_t LIST = 1024;
-    __shared__ uint32_t s_n, s_base, s_list[LIST];
-    if (threadIdx.x == 0) s_n = 0;
-    __syncthreads();
-    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-        if (keys[i] <= thr) {
-            const uint32_t p = atomicAdd(&s_n, 1u);
-            if (p < LIST) {
-                s_list[p] = i;
-            } else {
-                const uint32_t gp = atomicAdd(count, 1u);
-                if (gp < cap) slots[gp] = i;
-            }
-        }
-    __syncthreads();
-    const uint32_t m = s_n < LIST ? s_n : LIST;
-    if (threadIdx.x == 0 && m) s_base = atomicAdd(count, m);
-    __syncthreads();
-    for (uint32_t j = threadIdx.x; j < m; j += blockDim.x)
-        if (s_base + j < cap) slots[s_base + j] = s_list[j];
-}
-__global__ void k_gather_page(const int64_t *gids, const unsigned long long *keys, const uint32_t *slots, uint32_t m, int64_t *out_g,
-                              unsigned long long *out_k) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < m) {
-        out_g[i] = gids[slots[i]];
-        out_k[i] = keys[slots[i]];
-    }
-}
 // candidate group ids -> their slot in this branch (groups are stored in id order) and window key; absent: slot = ~0
 __global__ void k_cand_lookup(const int64_t *gids, const unsigned long long *keys, uint32_t n, const int64_t *cand, uint32_t m, uint32_t *slot,
                               unsigned long long *key) {
@@ -253,13 +216,8 @@ pvs_status pvs_digest_device(const void *d, uint64_t n, int word_bytes, uint64_t
 
 pvs_status pvs_rrf_window_keys(const double *d_vals, uint32_t n, int descending, unsigned long long *d_keys, hipStream_t s) {
     if (n == 0) return PVS_OK;
-    uint32_t *idx = nullptr;
-    HIP_TRY(pvs_scratch_alloc((void **)&idx, (size_t)n * 4));  // (k_rank_keys also writes the identity permutation)
-    hipLaunchKernelGGL(k_rank_keys, dim3(grid_for(n)), dim3(256), 0, s, d_vals, n, descending, d_keys, idx);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    pvs_scratch_free_on(idx, s);
-    if (e != hipSuccess) return pvs_fail(PVS_ERR_DEVICE, "window keys: %s", hipGetErrorString(e));
+    hipLaunchKernelGGL(k_rank_keys, dim3(grid_for(n)), dim3(256), 0, s, d_vals, n, descending, d_keys, nullptr);
+    HIP_TRY(hipGetLastError());
     return PVS_OK;
 }
 pvs_status pvs_rrf_window_keys_t(const double *d_vals_t, uint32_t n, uint32_t ncol, int descending, unsigned long long *d_keys, double *d_vals,
@@ -269,49 +227,6 @@ pvs_status pvs_rrf_window_keys_t(const double *d_vals_t, uint32_t n, uint32_t nc
     hipLaunchKernelGGL(k_window_keys_t, dim3((n + WKT_GROUPS - 1) / WKT_GROUPS), dim3(256), 0, s, d_vals_t, n, ncol, descending, d_keys, d_vals);
     HIP_TRY(hipGetLastError());
     return PVS_OK;
-}
-pvs_status pvs_rrf_sample_keys(const unsigned long long *d_keys, uint32_t n, uint32_t m, unsigned long long *h_out, hipStream_t s) {
-    unsigned long long *d = nullptr;
-    HIP_TRY(pvs_scratch_alloc((void **)&d, (size_t)m * 8));
-    hipLaunchKernelGGL(k_sample_keys, dim3((m + 255) / 256), dim3(256), 0, s, d_keys, n, m, d);
-    hipError_t e = hipMemcpyAsync(h_out, d, (size_t)m * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    pvs_scratch_free_on(d, s);
-    if (e != hipSuccess) return pvs_fail(PVS_ERR_DEVICE, "sample keys: %s", hipGetErrorString(e));
-    return PVS_OK;
-}
-// every group with key <= thr: (group id, key), any order; *out_count may exceed cap (then nothing is written)
-pvs_status pvs_rrf_page(const unsigned long long *d_keys, const int64_t *d_gids, uint32_t n, unsigned long long thr, uint32_t cap,
-                        int64_t *out_gids, unsigned long long *out_keys, uint32_t *out_count, hipStream_t s) {
-    uint32_t *d_cnt = nullptr, *d_slots = nullptr;
-    int64_t *d_g = nullptr;
-    unsigned long long *d_k = nullptr;
-    auto body = [&]() -> pvs_status {
-        HIP_TRY(pvs_scratch_alloc((void **)&d_cnt, 4));
-        HIP_TRY(pvs_scratch_alloc((void **)&d_slots, (size_t)std::max<uint32_t>(cap, 1) * 4));
-        HIP_TRY(hipMemsetAsync(d_cnt, 0, 4, s));
-        if (n) hipLaunchKernelGGL(k_page_compact, dim3(grid_for(n)), dim3(256), 0, s, d_keys, n, thr, cap, d_cnt, d_slots);
-        HIP_TRY(hipGetLastError());
-        uint32_t cnt = 0;
-        HIP_TRY(hipMemcpyAsync(&cnt, d_cnt, 4, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        *out_count = cnt;
-        if (cnt > cap || cnt == 0) return PVS_OK;
-        HIP_TRY(pvs_scratch_alloc((void **)&d_g, (size_t)cnt * 8));
-        HIP_TRY(pvs_scratch_alloc((void **)&d_k, (size_t)cnt * 8));
-        hipLaunchKernelGGL(k_gather_page, dim3((cnt + 255) / 256), dim3(256), 0, s, d_gids, d_keys, d_slots, cnt, d_g, d_k);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(out_gids, d_g, (size_t)cnt * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipMemcpyAsync(out_keys, d_k, (size_t)cnt * 8, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        return PVS_OK;
-    };
-    pvs_status st = body();
-    pvs_scratch_free_on(d_cnt, s);
-    pvs_scratch_free_on(d_slots, s);
-    pvs_scratch_free_on(d_g, s);
-    pvs_scratch_free_on(d_k, s);
-    return st;
 }
 constexpr uint32_t CNT_PAD = 32;  // words between the counters of two columns (one 128-byte line each)
 // The page step for `ncol` key columns at once ([ncol][n] keys, one threshold each): three host round trips for the whole batch
@@ -385,15 +300,17 @@ pvs_status pvs_rrf_pages_cols(const unsigned long long *d_keys, const int64_t *d
     auto body = [&]() -> pvs_status {
         HIP_TRY(pvs_scratch_alloc((void **)&d_cnt, (size_t)ncol * CNT_PAD * 4));
         HIP_TRY(pvs_scratch_alloc((void **)&d_thr, (size_t)ncol * 8));
-        HIP_TRY(pvs_scratch_alloc((void **)&d_slots, (size_t)ncol * cap * 4));
-        HIP_TRY(pvs_scratch_alloc((void **)&d_g, (size_t)ncol * cap * 8));
-        HIP_TRY(pvs_scratch_alloc((void **)&d_k, (size_t)ncol * cap * 8));
+        const size_t slots = (size_t)ncol * std::max<uint32_t>(cap, 1);  // (cap 0: only the counts are asked for)
+        HIP_TRY(pvs_scratch_alloc((void **)&d_slots, slots * 4));
+        HIP_TRY(pvs_scratch_alloc((void **)&d_g, slots * 8));
+        HIP_TRY(pvs_scratch_alloc((void **)&d_k, slots * 8));
         HIP_TRY(hipMemsetAsync(d_cnt, 0, (size_t)ncol * CNT_PAD * 4, s));
         HIP_TRY(hipMemcpyAsync(d_thr, h_thr, (size_t)ncol * 8, hipMemcpyHostToDevice, s));
         const unsigned gx = (unsigned)std::min<uint32_t>((n + 255) / 256, 1024);
-        hipLaunchKernelGGL(k_page_compact_cols, dim3(gx, ncol), dim3(256), 0, s, d_keys, n, d_thr, cap, d_cnt, d_slots);
-        hipLaunchKernelGGL(k_gather_page_cols, dim3((cap + 255) / 256 > 64 ? 64 : (cap + 255) / 256, ncol), dim3(256), 0, s, d_gids, d_keys, n, d_slots,
-                           d_cnt, cap, d_g, d_k);
+        if (n) hipLaunchKernelGGL(k_page_compact_cols, dim3(gx, ncol), dim3(256), 0, s, d_keys, n, d_thr, cap, d_cnt, d_slots);
+        if (cap)
+            hipLaunchKernelGGL(k_gather_page_cols, dim3((cap + 255) / 256 > 64 ? 64 : (cap + 255) / 256, ncol), dim3(256), 0, s, d_gids, d_keys, n,
+                               d_slots, d_cnt, cap, d_g, d_k);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy2DAsync(out_count, 4, d_cnt, (size_t)CNT_PAD * 4, 4, ncol, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));

@@ -1,8 +1,8 @@
 // pvs_rrf_batch.hip — C ABI of libpvs: pvs_rrf_search_batch, the PQL `or` arm for a batch of composed queries.  pvs_rrf_search
 // streams every byte of every branch for ONE composed query; here each branch is scored for up to 32 queries of the batch in one
 // corpus pass (the per-item scorers of pvs_search_groups), the window keys of the whole chunk come out of one launch per branch, and
-// the first round of the bounded fusion runs for the whole chunk at once on the device (one launch per step, one synchronisation);
-// each query then continues, where it must, over its own columns with the single-query fusion (pvs_rrf_search.hip) — so every page
+// the first round of the bounded fusion runs for the whole chunk at once on the device (rrf_round_device, the single call's round
+// with nq = the chunk: one launch per step, one synchronisation); each query then continues, where it must, over its own columns with the single-query fusion (pvs_rrf_search.hip) — so every page
 // is pvs_rrf_search's, bit for bit, without re-scoring the corpus.
 #include "pvs_rrf_search.hpp"
 
@@ -105,59 +105,6 @@ uint32_t first_chunk(const pvs_rrf_branch *br, uint32_t nb, uint32_t batch) {
     while (cq > 1 && need(cq) > budget) cq--;
     return cq;
 }
-
-// Round 0 of the bounded fusion for every query of a chunk on the device (pvs_rrf_round_device_batch): each step one launch for the
-// whole chunk, one synchronisation for all of it.  state[j]: 2 = the bound was met and query j's page is written, 1 = not met (the
-// query continues at round 1), 0 = a size limit of the device form was hit (round 0 again in host form) — each as
-// rrf_round_on_device decides for one query.
-pvs_status batched_round(const pvs_rrf_branch *br, uint32_t nb, const std::vector<BranchChunk> &ch, uint32_t nq, const PvsRrfParams &p, uint64_t target,
-                         uint32_t k, int64_t *out_groups, double *out_scores, uint32_t *out_counts, std::vector<uint8_t> &state) {
-    state.assign(nq, 0);
-    pvs_index *root = br[0].idx;
-    HIP_TRY(hipSetDevice(root->device));
-    hipStream_t s = root->search_stream;  // (the chunk's columns are complete: score_branch_chunk synchronised their streams)
-    std::vector<const unsigned long long *> keys((size_t)nq * nb);
-    const int64_t *gids[PVS_RRF_MAX_BRANCHES];
-    uint32_t n[PVS_RRF_MAX_BRANCHES];
-    for (uint32_t b = 0; b < nb; b++) {
-        n[b] = br[b].idx->n_groups;
-        gids[b] = br[b].idx->d_grp_ids;
-        for (uint32_t j = 0; j < nq; j++) keys[(size_t)j * nb + b] = ch[b].keys ? ch[b].keys + (size_t)j * n[b] : nullptr;
-    }
-    uint32_t t;
-    SearchCtx *c = ctx_acquire(root, &t);  // (its pinned block takes the chunk's pages)
-    void *d_work = nullptr;
-    auto body = [&]() -> pvs_status {
-        PVS_TRY(ctx_pinned_io(*c, pvs_rrf_round_device_batch_out_bytes(nb, k, nq)));
-        HIP_TRY(pvs_scratch_alloc(&d_work, pvs_rrf_round_device_batch_work_bytes(nb, nq)));
-        HIP_TRY(pvs_rrf_round_device_batch(nq, keys.data(), gids, n, nb, p, (uint32_t)target, k, d_work, c->h_io, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        const size_t stride = pvs_rrf_round_device_out_stride(nb, k);
-        for (uint32_t j = 0; j < nq; j++) {
-            uint32_t flags = 0, R[PVS_RRF_MAX_BRANCHES], m = 0, n_out = 0;
-            const int64_t *g = nullptr;
-            const double *sc = nullptr;
-            pvs_rrf_round_device_result(c->h_io + (size_t)j * stride, nb, k, &flags, R, &m, &n_out, &g, &sc);
-            if (flags) continue;
-            state[j] = 1;
-            double U = 0.0;  // the most a group outside every page can score (rrf_bounded)
-            for (uint32_t b = 0; b < nb; b++) U += p.w[b] / ((double)p.k[b] + (double)R[b] + 1.0);
-            U *= 1.0 + 1e-12;
-            if (m >= k && n_out == k && sc[k - 1] > U) {
-                memcpy(out_groups + (size_t)j * k, g, (size_t)k * 8);
-                memcpy(out_scores + (size_t)j * k, sc, (size_t)k * 8);
-                out_counts[j] = k;
-                state[j] = 2;
-            }
-        }
-        return PVS_OK;
-    };
-    pvs_status st = body();
-    if (st != PVS_OK) (void)hipStreamSynchronize(s);
-    pvs_scratch_free(d_work);
-    ctx_done(root, c);
-    return st;
-}
 }  // namespace
 
 // Row j of the outputs = pvs_rrf_search with every branch's query set to its j-th vector (see pvs.h)
@@ -218,8 +165,14 @@ PVS_EXPORT pvs_status pvs_rrf_search_batch(const pvs_rrf_branch *br, uint32_t nb
                 for (uint32_t b = 0; b < nb; b++) shape[b].n_groups = br[b].idx->n_groups;
                 target = rrf_device_round_target(shape, p, k);
             }
-            if (target)
-                PVS_TRY(batched_round(br, nb, ch, nq, p, target, k, out_groups + (size_t)q0 * k, out_scores + (size_t)q0 * k, out_counts + q0, state));
+            if (target) {
+                std::vector<const unsigned long long *> keys((size_t)nq * nb);
+                for (uint32_t j = 0; j < nq; j++)
+                    for (uint32_t b = 0; b < nb; b++) keys[(size_t)j * nb + b] = ch[b].keys ? ch[b].keys + (size_t)j * br[b].idx->n_groups : nullptr;
+                state.resize(nq);
+                PVS_TRY(rrf_round_device(br, nb, keys.data(), nq, p, target, k, out_groups + (size_t)q0 * k, out_scores + (size_t)q0 * k, out_counts + q0,
+                                         state.data(), nullptr));
+            }
             for (uint32_t j = 0; j < nq; j++) {
                 std::vector<RrfBranchCols> cols(nb);
                 for (uint32_t b = 0; b < nb; b++) {

@@ -3,8 +3,9 @@
 // `ORDER BY score DESC LIMIT k` (pql/builder.rs:757-771, 1284-1301) for the files that can reach the page.
 //
 // The host form of the round makes seven round trips (sample, page count, page, candidate keys, counts per branch; sorts on the host
-// in between): 0.9-1.2 ms of a 7.5-ms composed query at configs[4] for ~0.15 ms of kernels.  Here, on one stream behind the branches'
-// scoring:
+// in between): 0.9-1.2 ms of a 7.5-ms composed query at configs[4] for ~0.15 ms of kernels.  Here, for nq >= 1 queries at once
+// (pvs_rrf_search: one; pvs_rrf_search_batch: a chunk), on one stream behind the branches' scoring, every step one launch for all
+// of them:
 //   per branch   k_rd_threshold   sample of 8,192 window keys in LDS -> the key T_b at or below which ~1.5 x target files lie
 //                k_rd_compact     every file with key <= T_b -> a list of slots (any order)
 //                k_rd_cut         cut back to the files at or below the list's own target-th smallest key: the page, R_b files
@@ -409,39 +410,37 @@ __device__ __forceinline__ void rd_fuse(const RdArgs &a) {
     if (tid == 0) *a.out_n = nout;
 }
 
-// The kernels: one round of one query (RdArgs by value), and the same steps for a chunk of queries of a batch (pvs_rrf_search_batch):
-// per-query RdArgs in device memory, the query in blockIdx.y (k_rd_lookup: blockIdx.z; k_rd_compact / k_rd_count: blockIdx.z = branch)
-__global__ __launch_bounds__(1024) void k_rd_threshold(RdArgs a) { rd_threshold(a); }
-__global__ __launch_bounds__(1024) void k_rd_threshold_q(const RdArgs *__restrict__ qa) { rd_threshold(qa[blockIdx.y]); }
-__global__ __launch_bounds__(1024) void k_rd_cut(RdArgs a) { rd_cut(a); }
-__global__ __launch_bounds__(1024) void k_rd_cut_q(const RdArgs *__restrict__ qa) { rd_cut(qa[blockIdx.y]); }
-__global__ __launch_bounds__(1024) void k_rd_union(RdArgs a) { rd_union(a); }
-__global__ __launch_bounds__(1024) void k_rd_union_q(const RdArgs *__restrict__ qa) { rd_union(qa[blockIdx.y]); }
-__global__ __launch_bounds__(256) void k_rd_lookup(RdArgs a) { rd_lookup(a); }
-__global__ __launch_bounds__(256) void k_rd_lookup_q(const RdArgs *__restrict__ qa) { rd_lookup(qa[blockIdx.z]); }
-__global__ __launch_bounds__(1024) void k_rd_order(RdArgs a) { rd_order(a); }
-__global__ __launch_bounds__(1024) void k_rd_order_q(const RdArgs *__restrict__ qa) { rd_order(qa[blockIdx.y]); }
-__global__ __launch_bounds__(1024) void k_rd_ranks(RdArgs a) { rd_ranks(a); }
-__global__ __launch_bounds__(1024) void k_rd_ranks_q(const RdArgs *__restrict__ qa) { rd_ranks(qa[blockIdx.y]); }
-__global__ __launch_bounds__(1024) void k_rd_fuse(RdArgs a) { rd_fuse(a); }
-__global__ __launch_bounds__(1024) void k_rd_fuse_q(const RdArgs *__restrict__ qa) { rd_fuse(qa[blockIdx.y]); }
-__global__ __launch_bounds__(256) void k_rd_compact(RdBranch b) { rd_compact(b); }
-__global__ __launch_bounds__(256) void k_rd_compact_q(const RdArgs *__restrict__ qa) { rd_compact(qa[blockIdx.y].br[blockIdx.z]); }
-__global__ __launch_bounds__(1024) void k_rd_count(RdBranch b) { rd_count(b); }
-__global__ __launch_bounds__(1024) void k_rd_count_q(const RdArgs *__restrict__ qa) { rd_count(qa[blockIdx.y].br[blockIdx.z]); }
+// The kernels: per-query RdArgs in device memory, the query in blockIdx.y (k_rd_lookup: blockIdx.z; k_rd_compact / k_rd_count:
+// blockIdx.z = branch)
+__global__ __launch_bounds__(1024) void k_rd_threshold(const RdArgs *__restrict__ qa) { rd_threshold(qa[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_rd_cut(const RdArgs *__restrict__ qa) { rd_cut(qa[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_rd_union(const RdArgs *__restrict__ qa) { rd_union(qa[blockIdx.y]); }
+__global__ __launch_bounds__(256) void k_rd_lookup(const RdArgs *__restrict__ qa) { rd_lookup(qa[blockIdx.z]); }
+__global__ __launch_bounds__(1024) void k_rd_order(const RdArgs *__restrict__ qa) { rd_order(qa[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_rd_ranks(const RdArgs *__restrict__ qa) { rd_ranks(qa[blockIdx.y]); }
+__global__ __launch_bounds__(1024) void k_rd_fuse(const RdArgs *__restrict__ qa) { rd_fuse(qa[blockIdx.y]); }
+__global__ __launch_bounds__(256) void k_rd_compact(const RdArgs *__restrict__ qa) { rd_compact(qa[blockIdx.y].br[blockIdx.z]); }
+__global__ __launch_bounds__(1024) void k_rd_count(const RdArgs *__restrict__ qa) { rd_count(qa[blockIdx.y].br[blockIdx.z]); }
 
 size_t al(size_t x) { return (x + 255) & ~(size_t)255; }
+// one query's work arrays (its page counters live apart, side by side with the other queries')
+size_t query_work_bytes(uint32_t nb) {
+    const size_t per = al(8) + al(RD_CUT * 4) + al(RD_PAGE * 8) + al(RD_CAND * 4) + al(RD_CAND * 8) * 3 + al(RD_CAND * 4) + al(4) + al((RD_CAND + 1) * 8) + al(RD_CAND * 8);
+    return al(per * nb + al(RD_CAND * 8) + al(4));
+}
 std::atomic<bool> g_rd_configured{false};
 }  // namespace
 
 bool pvs_rrf_round_device_supported(uint32_t nb, uint64_t target, uint32_t k) {
     return nb >= 1 && nb <= (uint32_t)PVS_RRF_MAX_BRANCHES && target <= RD_PAGE / 2 && (uint64_t)nb * target <= RD_CAND && k <= RD_CAND;
 }
-size_t pvs_rrf_round_device_work_bytes(uint32_t nb) {
-    const size_t per = al(8) + al(4) + al(RD_CUT * 4) + al(RD_PAGE * 8) + al(RD_CAND * 4) + al(RD_CAND * 8) * 3 + al(RD_CAND * 4) + al(4) + al((RD_CAND + 1) * 8) + al(RD_CAND * 8);
-    return per * nb + al(RD_CAND * 8) + al(4) + 256;
+size_t pvs_rrf_round_device_out_stride(uint32_t nb, uint32_t k) { return al(64 + al((size_t)nb * 4) + al((size_t)k * 8) * 2 + 256); }
+size_t pvs_rrf_round_device_work_bytes(uint32_t nb, uint32_t nq) {
+    return al((size_t)nq * nb * 4) + (size_t)nq * query_work_bytes(nb) + al((size_t)nq * sizeof(RdArgs));
 }
-size_t pvs_rrf_round_device_out_bytes(uint32_t nb, uint32_t k) { return 64 + al((size_t)nb * 4) + al((size_t)k * 8) * 2 + 256; }
+size_t pvs_rrf_round_device_out_bytes(uint32_t nb, uint32_t k, uint32_t nq) {
+    return (size_t)nq * pvs_rrf_round_device_out_stride(nb, k) + al((size_t)nq * sizeof(RdArgs));
+}
 
 static hipError_t rd_configure() {
     if (!g_rd_configured.load(std::memory_order_acquire)) {
@@ -451,101 +450,18 @@ static hipError_t rd_configure() {
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_order, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 20);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_count, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 20 + 16);
         if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_fuse, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 24);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_threshold_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_M * 8);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_cut_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CUT * 8);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_union_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 12);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_order_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 20);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_count_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 20 + 16);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)k_rd_fuse_q, hipFuncAttributeMaxDynamicSharedMemorySize, RD_CAND * 24);
         if (e != hipSuccess) return e;
         g_rd_configured.store(true, std::memory_order_release);
     }
     return hipSuccess;
 }
 
-// One round on stream s (which already waits for the branches' window keys).  h_out: a pinned, device-mapped block of
-// pvs_rrf_round_device_out_bytes; the caller synchronises s and reads it with pvs_rrf_round_device_result.
-hipError_t pvs_rrf_round_device(const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb, const PvsRrfParams &p,
-                                uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s) {
-    if (hipError_t e = rd_configure(); e != hipSuccess) return e;
-    RdArgs a;
-    memset(&a, 0, sizeof a);
-    a.nb = nb;
-    a.target = target;
-    a.k = k;
-    a.p = p;
-    uint8_t *w = (uint8_t *)d_work;
-    auto take = [&](size_t bytes) {
-        uint8_t *r = w;
-        w += al(bytes);
-        return r;
-    };
-    for (uint32_t b = 0; b < nb; b++) {
-        RdBranch &r = a.br[b];
-        r.keys = d_keys[b];
-        r.gids = d_gids[b];
-        r.n = n[b];
-        r.thr = (unsigned long long *)take(8);
-        r.cnt = (uint32_t *)take(4);
-        r.slots = (uint32_t *)take(RD_CUT * 4);
-        r.page_g = (int64_t *)take(RD_PAGE * 8);
-        r.cslot = (uint32_t *)take(RD_CAND * 4);
-        r.ckey = (unsigned long long *)take(RD_CAND * 8);
-        r.ok = (unsigned long long *)take(RD_CAND * 8);
-        r.og = (int64_t *)take(RD_CAND * 8);
-        r.oi = (uint32_t *)take(RD_CAND * 4);
-        r.mp = (uint32_t *)take(4);
-        r.hist = (unsigned long long *)take((RD_CAND + 1) * 8);
-        r.rank = (int64_t *)take(RD_CAND * 8);
-    }
-    a.cand = (int64_t *)take(RD_CAND * 8);
-    a.m = (uint32_t *)take(4);
-    uint8_t *o = h_out;
-    a.flags = (uint32_t *)o;
-    a.out_m = (uint32_t *)(o + 16);
-    a.out_n = (uint32_t *)(o + 32);
-    a.R = (uint32_t *)(o + 64);
-    a.out_g = (int64_t *)(o + 64 + al((size_t)nb * 4));
-    a.out_s = (double *)((uint8_t *)a.out_g + al((size_t)k * 8));
-    *(volatile uint32_t *)a.flags = 0;
-    *(volatile uint32_t *)a.out_m = 0;
-    *(volatile uint32_t *)a.out_n = 0;
-    for (uint32_t b = 0; b < nb; b++) {
-        hipError_t e = hipMemsetAsync(a.br[b].cnt, 0, 4, s);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(k_rd_threshold, dim3(nb), dim3(RD_T), RD_M * 8, s, a);
-    for (uint32_t b = 0; b < nb; b++)
-        if (a.br[b].n) {
-            const unsigned g = (unsigned)std::min<uint64_t>(((uint64_t)a.br[b].n + 255) / 256, 2048);
-            hipLaunchKernelGGL(k_rd_compact, dim3(g), dim3(256), 0, s, a.br[b]);
-        }
-    hipLaunchKernelGGL(k_rd_cut, dim3(nb), dim3(RD_T), RD_CUT * 8, s, a);
-    hipLaunchKernelGGL(k_rd_union, dim3(1), dim3(RD_T), RD_CAND * 12, s, a);
-    hipLaunchKernelGGL(k_rd_lookup, dim3(RD_CAND / 256, nb), dim3(256), 0, s, a);
-    hipLaunchKernelGGL(k_rd_order, dim3(nb), dim3(RD_T), RD_CAND * 20, s, a);
-    for (uint32_t b = 0; b < nb; b++)
-        if (a.br[b].n) {
-            const unsigned g = (unsigned)std::min<uint64_t>(((uint64_t)a.br[b].n + RD_T - 1) / RD_T, 256);
-            hipLaunchKernelGGL(k_rd_count, dim3(g), dim3(RD_T), RD_CAND * 20 + 16, s, a.br[b]);
-        }
-    hipLaunchKernelGGL(k_rd_ranks, dim3(nb), dim3(RD_T), 0, s, a);
-    hipLaunchKernelGGL(k_rd_fuse, dim3(1), dim3(RD_T), RD_CAND * 24, s, a);
-    return hipGetLastError();
-}
-
-// pvs_rrf_search_batch: one round for each of nq queries, every step ONE launch for the whole chunk, one synchronisation for all
-// (the caller's).  d_keys[q * nb + b]: query q's window keys in branch b (the branch's file ids and count are shared).  Query q's
-// output lands at h_out + q * pvs_rrf_round_device_out_stride(nb, k), read with pvs_rrf_round_device_result.
-size_t pvs_rrf_round_device_out_stride(uint32_t nb, uint32_t k) { return al(pvs_rrf_round_device_out_bytes(nb, k)); }
-size_t pvs_rrf_round_device_batch_work_bytes(uint32_t nb, uint32_t nq) {
-    return al((size_t)nq * nb * 4) + (size_t)nq * al(pvs_rrf_round_device_work_bytes(nb)) + al((size_t)nq * sizeof(RdArgs));
-}
-size_t pvs_rrf_round_device_batch_out_bytes(uint32_t nb, uint32_t k, uint32_t nq) {
-    return (size_t)nq * pvs_rrf_round_device_out_stride(nb, k) + al((size_t)nq * sizeof(RdArgs));
-}
-hipError_t pvs_rrf_round_device_batch(uint32_t nq, const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb,
-                                      const PvsRrfParams &p, uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s) {
+// One round for each of nq queries on stream s (which already waits for the branches' window keys), every step ONE launch for all of
+// them.  d_keys[q * nb + b]: query q's window keys in branch b (the branch's file ids and count are shared).  d_work and h_out (pinned,
+// device-mapped) hold pvs_rrf_round_device_work_bytes / _out_bytes; the caller synchronises s and reads query q's output at
+// h_out + q * pvs_rrf_round_device_out_stride(nb, k) with pvs_rrf_round_device_result.
+hipError_t pvs_rrf_round_device(uint32_t nq, const unsigned long long *const *d_keys, const int64_t *const *d_gids, const uint32_t *n, uint32_t nb,
+                                const PvsRrfParams &p, uint32_t target, uint32_t k, void *d_work, uint8_t *h_out, hipStream_t s) {
     if (nq == 0) return hipSuccess;
     if (hipError_t e = rd_configure(); e != hipSuccess) return e;
     uint8_t *w = (uint8_t *)d_work;
@@ -560,7 +476,7 @@ hipError_t pvs_rrf_round_device_batch(uint32_t nq, const unsigned long long *con
         a.target = target;
         a.k = k;
         a.p = p;
-        uint8_t *wq = w + (size_t)q * al(pvs_rrf_round_device_work_bytes(nb));
+        uint8_t *wq = w + (size_t)q * query_work_bytes(nb);
         auto take = [&](size_t bytes) {
             uint8_t *r = wq;
             wq += al(bytes);
@@ -572,7 +488,6 @@ hipError_t pvs_rrf_round_device_batch(uint32_t nq, const unsigned long long *con
             r.gids = d_gids[b];
             r.n = n[b];
             r.thr = (unsigned long long *)take(8);
-            (void)take(4);
             r.cnt = cnt + (size_t)q * nb + b;
             r.slots = (uint32_t *)take(RD_CUT * 4);
             r.page_g = (int64_t *)take(RD_PAGE * 8);
@@ -598,7 +513,7 @@ hipError_t pvs_rrf_round_device_batch(uint32_t nq, const unsigned long long *con
         *(volatile uint32_t *)a.out_m = 0;
         *(volatile uint32_t *)a.out_n = 0;
     }
-    RdArgs *d_args = (RdArgs *)(w + (size_t)nq * al(pvs_rrf_round_device_work_bytes(nb)));
+    RdArgs *d_args = (RdArgs *)(w + (size_t)nq * query_work_bytes(nb));
     hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nq * nb * 4, s);
     if (e == hipSuccess) e = hipMemcpyAsync(d_args, h_args, (size_t)nq * sizeof(RdArgs), hipMemcpyHostToDevice, s);
     if (e != hipSuccess) return e;
@@ -607,15 +522,15 @@ hipError_t pvs_rrf_round_device_batch(uint32_t nq, const unsigned long long *con
         gc = std::max<unsigned>(gc, (unsigned)std::min<uint64_t>(((uint64_t)n[b] + 255) / 256, 2048));
         gn = std::max<unsigned>(gn, (unsigned)std::min<uint64_t>(((uint64_t)n[b] + RD_T - 1) / RD_T, 256));
     }
-    hipLaunchKernelGGL(k_rd_threshold_q, dim3(nb, nq), dim3(RD_T), RD_M * 8, s, d_args);
-    hipLaunchKernelGGL(k_rd_compact_q, dim3(gc, nq, nb), dim3(256), 0, s, d_args);
-    hipLaunchKernelGGL(k_rd_cut_q, dim3(nb, nq), dim3(RD_T), RD_CUT * 8, s, d_args);
-    hipLaunchKernelGGL(k_rd_union_q, dim3(1, nq), dim3(RD_T), RD_CAND * 12, s, d_args);
-    hipLaunchKernelGGL(k_rd_lookup_q, dim3(RD_CAND / 256, nb, nq), dim3(256), 0, s, d_args);
-    hipLaunchKernelGGL(k_rd_order_q, dim3(nb, nq), dim3(RD_T), RD_CAND * 20, s, d_args);
-    hipLaunchKernelGGL(k_rd_count_q, dim3(gn, nq, nb), dim3(RD_T), RD_CAND * 20 + 16, s, d_args);
-    hipLaunchKernelGGL(k_rd_ranks_q, dim3(nb, nq), dim3(RD_T), 0, s, d_args);
-    hipLaunchKernelGGL(k_rd_fuse_q, dim3(1, nq), dim3(RD_T), RD_CAND * 24, s, d_args);
+    hipLaunchKernelGGL(k_rd_threshold, dim3(nb, nq), dim3(RD_T), RD_M * 8, s, d_args);
+    hipLaunchKernelGGL(k_rd_compact, dim3(gc, nq, nb), dim3(256), 0, s, d_args);
+    hipLaunchKernelGGL(k_rd_cut, dim3(nb, nq), dim3(RD_T), RD_CUT * 8, s, d_args);
+    hipLaunchKernelGGL(k_rd_union, dim3(1, nq), dim3(RD_T), RD_CAND * 12, s, d_args);
+    hipLaunchKernelGGL(k_rd_lookup, dim3(RD_CAND / 256, nb, nq), dim3(256), 0, s, d_args);
+    hipLaunchKernelGGL(k_rd_order, dim3(nb, nq), dim3(RD_T), RD_CAND * 20, s, d_args);
+    hipLaunchKernelGGL(k_rd_count, dim3(gn, nq, nb), dim3(RD_T), RD_CAND * 20 + 16, s, d_args);
+    hipLaunchKernelGGL(k_rd_ranks, dim3(nb, nq), dim3(RD_T), 0, s, d_args);
+    hipLaunchKernelGGL(k_rd_fuse, dim3(1, nq), dim3(RD_T), RD_CAND * 24, s, d_args);
     return hipGetLastError();
 }
 // after the stream drained: flags != 0 -> the round must be redone by the host form

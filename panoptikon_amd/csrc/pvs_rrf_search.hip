@@ -144,7 +144,7 @@ PVS_EXPORT pvs_status pvs_rrf_cols_threshold(pvs_rrf_cols *c, uint64_t target_gr
     HIP_TRY(hipSetDevice(c->ix->device));
     if (c->sample.empty()) {
         c->sample.resize(M);
-        PVS_TRY(pvs_rrf_sample_keys(c->d_keys, c->n_groups, M, c->sample.data(), c->ix->search_stream));
+        PVS_TRY(pvs_rrf_sample_keys_cols(c->d_keys, c->n_groups, 1, M, c->sample.data(), c->ix->search_stream));
     }
     uint64_t j = (uint64_t)((double)M * 1.5 * (double)target_groups / (double)c->n_groups) + 1;
     if (j >= M) j = M - 1;
@@ -157,7 +157,9 @@ PVS_EXPORT pvs_status pvs_rrf_cols_page(pvs_rrf_cols *c, uint64_t key, uint32_t 
     *out_count = 0;
     if (c->n_groups == 0) return PVS_OK;
     HIP_TRY(hipSetDevice(c->ix->device));
-    return pvs_rrf_page(c->d_keys, c->ix->d_grp_ids, c->n_groups, key, cap, out_gids, (unsigned long long *)out_keys, out_count, c->ix->search_stream);
+    const unsigned long long thr = key;
+    return pvs_rrf_pages_cols(c->d_keys, c->ix->d_grp_ids, c->n_groups, 1, &thr, cap, out_gids, (unsigned long long *)out_keys, out_count,
+                              c->ix->search_stream);
 }
 PVS_EXPORT pvs_status pvs_rrf_cols_lookup(pvs_rrf_cols *c, const int64_t *gids, uint32_t m, uint64_t *out_keys, uint8_t *out_present) {
     if (!c || (m && (!gids || !out_keys || !out_present))) return pvs_fail(PVS_ERR_INVALID_ARG, "null argument");
@@ -215,17 +217,19 @@ struct RrfTrace {
         t0 = t1;
     }
 };
-// One round of the bounded fusion on the device (pvs_rrf_device.hip): pages, union, exact ranks, fused scores and the first k on
-// one stream behind the branches' scoring, one synchronisation.  *usable = false: a size limit of the device form was hit (a
-// flag) — the host form redoes the round.  Otherwise R[] holds the page sizes and, when the bound is met, the page is written.
-static pvs_status rrf_round_on_device(const pvs_rrf_branch *br, std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint64_t target, uint32_t k,
-                                      int64_t *out_groups, double *out_scores, uint32_t *out_count, bool *usable, bool *done, uint32_t *out_m) {
-    *usable = false;
-    const uint32_t nb = p.n_branches;
+// the most a group outside every page can score, R[b] groups on branch b's page (absent from a branch: an even smaller term)
+static double rrf_outside_bound(const PvsRrfParams &p, const uint32_t *R) {
+    double U = 0.0;
+    for (uint32_t b = 0; b < p.n_branches; b++) U += p.w[b] / ((double)p.k[b] + (double)R[b] + 1.0);
+    return U * (1.0 + 1e-12);
+}
+
+pvs_status rrf_round_device(const pvs_rrf_branch *br, uint32_t nb, const unsigned long long *const *keys, uint32_t nq, const PvsRrfParams &p,
+                            uint64_t target, uint32_t k, int64_t *out_groups, double *out_scores, uint32_t *out_counts, uint8_t *state, uint32_t *out_m) {
+    for (uint32_t j = 0; j < nq; j++) state[j] = 0;
     pvs_index *root = br[0].idx;
     HIP_TRY(hipSetDevice(root->device));
     hipStream_t s = root->search_stream;
-    const unsigned long long *keys[PVS_RRF_MAX_BRANCHES];
     const int64_t *gids[PVS_RRF_MAX_BRANCHES];
     uint32_t n[PVS_RRF_MAX_BRANCHES];
     std::vector<hipEvent_t> evs;
@@ -234,10 +238,9 @@ static pvs_status rrf_round_on_device(const pvs_rrf_branch *br, std::vector<RrfB
     void *d_work = nullptr;
     auto body = [&]() -> pvs_status {
         for (uint32_t b = 0; b < nb; b++) {
-            keys[b] = cols[b].d_keys;
             gids[b] = br[b].idx->d_grp_ids;
-            n[b] = cols[b].n_groups;
-            if (br[b].idx->search_stream != s) {  // the branch's keys are queued on its own index's stream
+            n[b] = br[b].idx->n_groups;
+            if (br[b].idx->search_stream != s) {  // the branch's keys may be queued on its own index's stream
                 hipEvent_t e;
                 HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
                 evs.push_back(e);
@@ -245,25 +248,25 @@ static pvs_status rrf_round_on_device(const pvs_rrf_branch *br, std::vector<RrfB
                 HIP_TRY(hipStreamWaitEvent(s, e, 0));
             }
         }
-        PVS_TRY(ctx_pinned_io(*c, pvs_rrf_round_device_out_bytes(nb, k)));
-        HIP_TRY(pvs_scratch_alloc(&d_work, pvs_rrf_round_device_work_bytes(nb)));
-        HIP_TRY(pvs_rrf_round_device(keys, gids, n, nb, p, (uint32_t)target, k, d_work, c->h_io, s));
+        PVS_TRY(ctx_pinned_io(*c, pvs_rrf_round_device_out_bytes(nb, k, nq)));
+        HIP_TRY(pvs_scratch_alloc(&d_work, pvs_rrf_round_device_work_bytes(nb, nq)));
+        HIP_TRY(pvs_rrf_round_device(nq, keys, gids, n, nb, p, (uint32_t)target, k, d_work, c->h_io, s));
         HIP_TRY(hipStreamSynchronize(s));
-        uint32_t flags = 0, R[PVS_RRF_MAX_BRANCHES], m = 0, n_out = 0;
-        const int64_t *g = nullptr;
-        const double *sc = nullptr;
-        pvs_rrf_round_device_result(c->h_io, nb, k, &flags, R, &m, &n_out, &g, &sc);
-        if (flags) return PVS_OK;
-        *usable = true;
-        *out_m = m;
-        double U = 0.0;  // the most a group outside every page can score (rrf_bounded)
-        for (uint32_t b = 0; b < nb; b++) U += p.w[b] / ((double)p.k[b] + (double)R[b] + 1.0);
-        U *= 1.0 + 1e-12;
-        if (m >= k && n_out == k && sc[k - 1] > U) {
-            memcpy(out_groups, g, (size_t)k * 8);
-            memcpy(out_scores, sc, (size_t)k * 8);
-            *out_count = k;
-            *done = true;
+        const size_t stride = pvs_rrf_round_device_out_stride(nb, k);
+        for (uint32_t j = 0; j < nq; j++) {
+            uint32_t flags = 0, R[PVS_RRF_MAX_BRANCHES], m = 0, n_out = 0;
+            const int64_t *g = nullptr;
+            const double *sc = nullptr;
+            pvs_rrf_round_device_result(c->h_io + (size_t)j * stride, nb, k, &flags, R, &m, &n_out, &g, &sc);
+            if (out_m) out_m[j] = m;
+            if (flags) continue;
+            state[j] = 1;
+            if (m >= k && n_out == k && sc[k - 1] > rrf_outside_bound(p, R)) {
+                memcpy(out_groups + (size_t)j * k, g, (size_t)k * 8);
+                memcpy(out_scores + (size_t)j * k, sc, (size_t)k * 8);
+                out_counts[j] = k;
+                state[j] = 2;
+            }
         }
         return PVS_OK;
     };
@@ -318,13 +321,16 @@ static pvs_status rrf_bounded(const pvs_rrf_branch *br, std::vector<RrfBranchCol
         if (rrf_page_too_large(cols, nb, target)) return PVS_OK;  // a page that would hold a quarter of the branch: full ranking
         // the first round entirely on the device (the stage digests read the host form's intermediate results: that form then)
         if (round == 0 && device_round && !dig && !pvs_dbg(PVS_DBG_RRF_HOST_ROUNDS) && pvs_rrf_round_device_supported(nb, target, k)) {
-            bool usable = false;
+            const unsigned long long *keys[PVS_RRF_MAX_BRANCHES];
+            for (uint32_t b = 0; b < nb; b++) keys[b] = cols[b].d_keys;
+            uint8_t state = 0;
             uint32_t m = 0;
-            PVS_TRY(rrf_round_on_device(br, cols, p, target, k, out_groups, out_scores, out_count, &usable, done, &m));
+            PVS_TRY(rrf_round_device(br, nb, keys, 1, p, target, k, out_groups, out_scores, out_count, &state, &m));
             tr.lap("round on the device");
-            if (tr.on) fprintf(stderr, "[rrf] round 0 on the device: target %llu, %u candidates%s\n", (unsigned long long)target, m, usable ? "" : " (size limit: host form)");
+            if (tr.on) fprintf(stderr, "[rrf] round 0 on the device: target %llu, %u candidates%s\n", (unsigned long long)target, m, state ? "" : " (size limit: host form)");
+            *done = state == 2;
             if (*done) return PVS_OK;
-            if (usable) continue;  // the bound was not met: larger pages
+            if (state == 1) continue;  // the bound was not met: larger pages
         }
         std::vector<std::vector<int64_t>> page(nb);
         std::vector<uint8_t> overflow(nb, 0);
@@ -407,11 +413,7 @@ static pvs_status rrf_bounded(const pvs_rrf_branch *br, std::vector<RrfBranchCol
         std::sort(gs.begin(), gs.end(), [](const GS &a, const GS &b) { return a.s != b.s ? a.s > b.s : a.g < b.g; });  // score DESC, group id
         tr.lap("fuse");
         if (tr.on) fprintf(stderr, "[rrf] round %d: target %llu, %u candidates\n", round, (unsigned long long)target, m);
-        // the most a group outside every page can score (absent from a branch: an even smaller term)
-        double U = 0.0;
-        for (uint32_t b = 0; b < nb; b++) U += p.w[b] / ((double)p.k[b] + (double)R[b] + 1.0);
-        U *= 1.0 + 1e-12;
-        if (m >= k && gs[k - 1].s > U) {
+        if (m >= k && gs[k - 1].s > rrf_outside_bound(p, R.data())) {
             for (uint32_t i = 0; i < k; i++) {
                 out_groups[i] = gs[i].g;
                 out_scores[i] = gs[i].s;

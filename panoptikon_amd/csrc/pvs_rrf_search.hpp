@@ -1,5 +1,6 @@
 // pvs_rrf_search.hpp — the pieces of pvs_rrf_search (pvs_rrf_search.hip) that its batched form (pvs_rrf_batch.hip) shares: the
-// scored columns of a branch, the per-branch threads, the fusion of scored branches and the order-key page.
+// scored columns of a branch, the per-branch threads, round 0 of the bounded fusion on the device for nq >= 1 queries, the fusion of
+// scored branches and the order-key page.
 #pragma once
 #include <functional>
 #include <string>
@@ -61,7 +62,13 @@ pvs_status rrf_fuse_scored(const pvs_rrf_branch *br, std::vector<RrfBranchCols> 
 // device_round = false (a size limit of the device form was hit: round 0 in host form)
 pvs_status rrf_fuse_continue(const pvs_rrf_branch *br, std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k, int64_t *out_groups,
                              double *out_scores, uint32_t *out_count, int *path, int first_round, bool device_round);
-// The page target of round 0 when rrf_fuse_scored would run that round on the device (pvs_rrf_round_device), else 0
+// Round 0 of the bounded fusion for nq queries on the device (pvs_rrf_round_device): every step one launch for all of them, one
+// synchronisation.  keys[j * nb + b]: query j's window keys in branch b.  state[j]: 2 = the bound was met and query j's page is
+// written (out_*: [nq][k], out_counts[j]), 1 = not met (the query continues at round 1), 0 = a size limit of the device form was hit
+// (the host form redoes round 0).  out_m (may be null): each query's candidates.
+pvs_status rrf_round_device(const pvs_rrf_branch *br, uint32_t nb, const unsigned long long *const *keys, uint32_t nq, const PvsRrfParams &p,
+                            uint64_t target, uint32_t k, int64_t *out_groups, double *out_scores, uint32_t *out_counts, uint8_t *state, uint32_t *out_m);
+// The page target of round 0 when rrf_fuse_scored would run that round on the device (rrf_round_device), else 0
 uint64_t rrf_device_round_target(const std::vector<RrfBranchCols> &cols, const PvsRrfParams &p, uint32_t k);
 // true when a branch's rows carry order keys (pvs_index_set_order_keys): the page then goes through rrf_keyed_page
 bool rrf_branches_keyed(const pvs_rrf_branch *br, uint32_t nb);
