@@ -362,6 +362,7 @@ void ctx_release(SearchCtx &c) {
     pvs_group_work_release(c.gwork);
     if (c.done) hipEventDestroy(c.done);
     if (c.scanned) hipEventDestroy(c.scanned);
+    if (c.tail) hipEventDestroy(c.tail);
     if (c.preluded) hipEventDestroy(c.preluded);
     hipFree(c.d_loc_rec);
     hipFree(c.d_all_rec);
@@ -405,7 +406,12 @@ pvs_status ctx_prepare(pvs_index *ix, SearchCtx &c, uint32_t batch, uint32_t k, 
         c.stream = ix->search_stream;
     }
     c.cur_mask = nullptr;
+    if (c.tail_pending) {  // (a joined pass's second part of pass C may still read this context: SearchCtx.tail)
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.tail, 0));
+        c.tail_pending = false;
+    }
     if (!c.done) HIP_TRY(hipEventCreateWithFlags(&c.done, hipEventDisableTiming));
+    if (!c.tail) HIP_TRY(hipEventCreateWithFlags(&c.tail, hipEventDisableTiming));
     if (!c.scanned) HIP_TRY(hipEventCreateWithFlags(&c.scanned, hipEventDisableTiming));
     if (!c.preluded) HIP_TRY(hipEventCreateWithFlags(&c.preluded, hipEventDisableTiming));
     c.side_finalize = false;

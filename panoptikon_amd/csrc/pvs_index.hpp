@@ -22,6 +22,7 @@ struct PageSplit {
     int64_t *ids;
     float *dist;
     uint32_t *count, *h_flags, *h_seen;
+    hipEvent_t first_done;  // the first caller's done event: recorded behind pass C of queries [0, at), before the second part
 };
 
 struct TimedSpan {
@@ -39,6 +40,10 @@ struct SearchCtx {
     hipEvent_t preluded = nullptr;     // recorded behind the k-th select when query prep / pass A / the select run on the index's prelude stream
     hipEvent_t scanned = nullptr;      // recorded behind pass B when pass C runs on the index's side stream
     bool side_finalize = false;        // this search's pass C went to ix->fin_stream (c.done was recorded there)
+    // a joined pass whose second part of pass C (the partner's queries) still reads this context's buffers on ix->fin_stream after
+    // this context's own ticket completed: recorded behind that part; the context's next use waits for it (ctx_prepare)
+    hipEvent_t tail = nullptr;
+    bool tail_pending = false;
     bool busy = false;
     // (under ix->mu) a stream-ordered search whose pvs_wait work is being done right now (by its owner or by a writer draining the
     // index: pvs_gate.hip), and one a writer completed on its owner's behalf: pvs_wait hands fin_status / fin_err over and releases

@@ -197,6 +197,8 @@ struct FinalizeArgs {
     // a pass shared by two callers (pvs_search_device, joined tickets): queries [split, batch) belong to the second one — their
     // pages, counts and host verdicts go to its buffers at q - split; the device words (need_dense, cand_seen) stay at q
     uint32_t split = UINT32_MAX;
+    // the launch covers queries [q0, batch) only (a joined pass finalises its two callers' queries in two launches)
+    uint32_t q0 = 0;
     int64_t *out_ids2 = nullptr;
     float *out_dist2 = nullptr;
     uint32_t *out_count2 = nullptr, *h_flags2 = nullptr, *h_seen2 = nullptr;

@@ -318,6 +318,7 @@ struct FinK {
     uint32_t *h_flags, *h_seen;    // pinned host mirrors of need_dense / cand_seen (FinalizeArgs.h_flags), or nullptr
     const uint32_t *trank, *tinv;  // second sort key: tie rank of a row and its inverse (FinalizeArgs.trank)
     uint32_t split;                // queries >= split: the second caller's buffers (FinalizeArgs.split)
+    uint32_t q0;                   // query of workgroup 0 (FinalizeArgs.q0)
     int64_t *out_ids2;
     float *out_dist2;
     uint32_t *out_count2, *h_flags2, *h_seen2;
@@ -350,7 +351,7 @@ __global__ __launch_bounds__(256) void k_finalize(FinK a) {
     __shared__ uint32_t hist[256];
     __shared__ uint32_t s_misc_light[LIGHT ? 16 : 1];
     __shared__ unsigned long long s_sort_light[LIGHT ? FIN_SMALL_SORT : 1];
-    const uint32_t q = blockIdx.x;
+    const uint32_t q = a.q0 + blockIdx.x;
     uint32_t *const s_ub = LIGHT ? a.w_ub + (size_t)q * a.cand_cap : (uint32_t *)smem;                            // [CAND_CAP] sort keys of upper bounds
     uint32_t *const s_surv = LIGHT ? a.w_surv + (size_t)q * PVS_SURV_CAP : (uint32_t *)(smem + PVS_CAND_CAP * 4);  // [SURV_CAP] candidate slots
     uint32_t *const s_misc = LIGHT ? s_misc_light : (uint32_t *)(smem + PVS_CAND_CAP * 4) + PVS_SURV_CAP;          // [0]=survivor count, [2..5] select scratch
@@ -720,6 +721,7 @@ hipError_t pvs_launch_finalize(const FinalizeArgs &f, hipStream_t s) {
     k.h_flags = f.h_flags;
     k.h_seen = f.h_seen;
     k.split = f.split;
+    k.q0 = f.q0;
     k.out_ids2 = f.out_ids2;
     k.out_dist2 = f.out_dist2;
     k.out_count2 = f.out_count2;
@@ -750,14 +752,16 @@ hipError_t pvs_launch_finalize(const FinalizeArgs &f, hipStream_t s) {
         configured.store(true, std::memory_order_release);
     }
     if ((((uint64_t)f.dim * (f.dtype == PVS_I8 ? 1u : 4u)) + 63u & ~63ull) > (uint64_t)FIN_QMAX) return hipErrorInvalidValue;  // (no scan instance is that wide)
+    if (f.q0 >= f.batch) return hipErrorInvalidValue;
+    const uint32_t nwg = f.batch - f.q0;
     const bool light = f.w_ub && f.w_surv && f.w_sort;
     const size_t qlds = ((size_t)f.dim * 4 + 63) & ~(size_t)63;
 #define PVS_FIN_LAUNCH(kernel, lds)                                                                                  \
     do {                                                                                                             \
         if (f.ev_start || f.ev_stop)                                                                                 \
-            hipExtLaunchKernelGGL(kernel, dim3(f.batch), dim3(256), lds, s, f.ev_start, f.ev_stop, 0, k);            \
+            hipExtLaunchKernelGGL(kernel, dim3(nwg), dim3(256), lds, s, f.ev_start, f.ev_stop, 0, k);                \
         else                                                                                                         \
-            hipLaunchKernelGGL(kernel, dim3(f.batch), dim3(256), lds, s, k);                                         \
+            hipLaunchKernelGGL(kernel, dim3(nwg), dim3(256), lds, s, k);                                             \
     } while (0)
     if (light && f.dtype == PVS_I8)
         PVS_FIN_LAUNCH((k_finalize<PVS_I8, true>), 0);

@@ -97,12 +97,18 @@ static pvs_status enqueue_fast_chunk(pvs_index *ix, SearchCtx &c, uint32_t qoff,
     // a handful of queries emit so little that 1/64 is enough.  The candidate list of a query
     // holds ~k/frac rows: keep that 2.5x below its capacity.
     double frac = nb <= 4 ? 1.0 / 32.0 : 1.0 / 16.0;  // (single query, 10M rows: 1/64 leaves pass C 6,400 candidates = 100 us (f16) for 10 us of pass A)
+    // The 256-query pass (k_scan_wide's half-size segment lists; a pipelined caller's joined pair) pays more per emitted candidate:
+    // a sample of 1/8 with the threshold at its (k/8)-th value costs pass A what 1/16 at k/4 does (~48 us at 10M rows) and halves the
+    // candidates (1,650 -> 935 per query at configs[2]): pass B 1.82 instead of 1.85 ms, pass C 32 instead of 40 us, the step
+    // 0.982-0.985 ms instead of 1.002-1.008 (same box, alternating; 1/8 at k/4: 0.998, 1/6 or 1/4 at k/8: 0.989-1.003).
+    const bool wide_pass = batch_pad == 256;
+    if (wide_pass) frac = 1.0 / 8.0;
     if (pvs_dbg(PVS_DBG_SAMPLE_DIV) > 0) frac = 1.0 / (double)pvs_dbg(PVS_DBG_SAMPLE_DIV);  // tuning experiments
     // The threshold need not be the sample's k-th value: its j-th value (j < k) from a sample j/k the size expects the same number
     // of candidates (j / frac') at j/k of pass A's cost, with a relative spread of 1/sqrt(j).  What is lost is the guarantee that k
     // rows lie below T — pass C certifies that from the candidates' upper bounds (FinalizeArgs.thr) and hands the query to the
     // dense path otherwise (never seen: it needs T below the corpus' k-th value while j sample rows lie below it).
-    const uint32_t j_div = pvs_dbg(PVS_DBG_SAMPLE_J_DIV) > 0 ? (uint32_t)pvs_dbg(PVS_DBG_SAMPLE_J_DIV) : 4u;  // tuning experiments
+    const uint32_t j_div = pvs_dbg(PVS_DBG_SAMPLE_J_DIV) > 0 ? (uint32_t)pvs_dbg(PVS_DBG_SAMPLE_J_DIV) : wide_pass ? 8u : 4u;  // tuning experiments
     uint32_t k_sel = k;
     if (ix->n >= (1ull << 18) && !flat_rerun) k_sel = std::min(k, std::max<uint32_t>(8, k / j_div));
     frac *= (double)k_sel / (double)k;
@@ -236,13 +242,33 @@ static pvs_status enqueue_fast_chunk(pvs_index *ix, SearchCtx &c, uint32_t qoff,
         fs = ix->fin_stream;
         c.side_finalize = true;
     }
+    // A joined pass completes per ticket: pass C of the first caller's queries [0, at) runs on the search's own stream right behind
+    // pass B (no cross-queue wait, the LDS finaliser: nothing else runs there until its caller's next submit) and its done event
+    // (split->first_done) is recorded behind it; the second caller's queries go where a lone search's pass C goes (the side stream
+    // when `side`), at the same time.  The first caller's pvs_wait returns while the second part still runs; the first part's
+    // launch is one workgroup per query like the whole one, so it takes what a 128-query pass C takes, not twice that.
+    FinalizeArgs f1 = f;
+    hipStream_t fs1 = fs;
+    if (split && split->first_done) {
+        f1.batch = split->at;
+        if (!ix->multi_stream && !force_light) {
+            f1.w_ub = f1.w_surv = nullptr;
+            f1.w_sort = nullptr;
+        }
+        fs1 = c.stream;
+        f.q0 = split->at;
+    }
     if (bound_ev) {
-        (void)span_bound(ix, c, 2, 0, &f.ev_start, &f.ev_stop);
-        HIP_TRY(pvs_launch_finalize(f, fs));
+        (void)span_bound(ix, c, 2, 0, &f1.ev_start, &f1.ev_stop);
+        HIP_TRY(pvs_launch_finalize(f1, fs1));
     } else {
-        span_begin(ix, c, 2, 0, fs);
+        span_begin(ix, c, 2, 0, fs1);
+        HIP_TRY(pvs_launch_finalize(f1, fs1));
+        span_end(ix, c, fs1);
+    }
+    if (split && split->first_done) {
+        HIP_TRY(hipEventRecord(split->first_done, c.stream));
         HIP_TRY(pvs_launch_finalize(f, fs));
-        span_end(ix, c, fs);
     }
     return PVS_OK;
 }
@@ -324,14 +350,15 @@ pvs_status prep_slot(pvs_index *ix, SearchCtx &c, const void *d_queries, int qdt
 }
 
 // Passes A / B / C of a held group (pvs_search_device.hip): nb prepared queries in context c, the first caller's pages to oid / od /
-// oc, the second caller's (split, or nullptr for a lone ticket) to its own buffers.  c.done is recorded behind pass C.
+// oc, the second caller's (split, or nullptr for a lone ticket) to its own buffers.  c.done is recorded behind pass C (split: behind
+// the part of pass C over the first caller's queries, split->first_done = c.done).
 pvs_status enqueue_joined_pass(pvs_index *ix, SearchCtx &c, uint32_t nb, uint32_t k, int metric, int64_t *oid, float *od, uint32_t *oc,
                                const PageSplit *split) {
     const uint32_t batch_pad = nb <= 32 ? 32 : nb <= 64 ? 64 : nb <= 128 ? 128 : 256;
     const bool side = !ix->multi_stream && c.stream == ix->search_stream && !pvs_dbg(PVS_DBG_NO_SIDE_FINALIZE);
     c.side_finalize = false;
     PVS_TRY(enqueue_fast_chunk(ix, c, 0, nb, batch_pad, k, metric, oid, od, oc, false, side, nullptr, split));
-    HIP_TRY(hipEventRecord(c.done, c.side_finalize ? ix->fin_stream : c.stream));
+    if (!split) HIP_TRY(hipEventRecord(c.done, c.side_finalize ? ix->fin_stream : c.stream));  // (split: behind the first part of pass C)
     return PVS_OK;
 }
 
@@ -410,9 +437,15 @@ pvs_status search_fallbacks(pvs_index *ix, SearchCtx &c, const void *d_queries, 
                                    int metric, int64_t *d_out_ids, float *d_out_dist, uint32_t *d_out_count) {
     uint32_t n_dense = 0, n_rerun = 0;
     uint64_t seen = 0;
+    bool any_flag = false;
     for (uint32_t q = 0; q < batch; q++) {
         n_rerun += c.h_need_dense[q] == 2 ? 1 : 0;
         seen += c.h_need_dense[c.flags_cap + q];
+        any_flag |= c.h_need_dense[q] != 0;
+    }
+    if (any_flag && c.tail_pending) {  // (the partner's part of a joined pass C may still read this context: SearchCtx.tail)
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.tail, 0));
+        c.tail_pending = false;
     }
     if (n_rerun && fast_path_ok(ix, k)) {
         // A candidate segment overflowed although the query's candidates fit one list (ties clustered in a few tile streams):

@@ -14,8 +14,10 @@
 // its queries prepped at submit, in stream order as before, and is HELD (pvs_index::join); the next compatible search preps its
 // queries into the slots behind them and launches the pair: pass A, the k-th select and pass B over all of them, pass C writing
 // every query's page, count and verdict into its own caller's buffers (FinalizeArgs.split).  Each ticket then completes on its
-// own: its done event is recorded behind the shared pass C, its fallbacks (the queries pass C handed back) run at its pvs_wait
-// over its own queries.  Every page is the one the same passes give a 256-query batch: the same exact values and order.
+// own: pass C runs as two launches, the held ticket's queries first on the search stream with its done event behind them, the
+// partner's at the same time on the side stream (enqueue_fast_chunk), so that the held ticket's pvs_wait — and its caller's next
+// submit — does not wait for the partner's pages; its fallbacks (the queries pass C handed back) run at its pvs_wait over its own
+// queries.  The held context's next use waits for the partner's part (SearchCtx.tail).  Every page is the one the same passes give a 256-query batch: the same exact values and order.
 // A held group is launched alone when its ticket is waited on, when anything needs stream order (a search that is not held,
 // pvs_sync, the profile, a writer at the gate, destroy), or when the window (pvs_debug "join_us", 0 = never hold) expires.
 static bool join_applies(pvs_index *ix, uint32_t batch, uint32_t k) {
@@ -44,9 +46,15 @@ static pvs_status join_launch_locked(pvs_index *ix, const JoinPartner *p) {
     auto body = [&]() -> pvs_status {
         HIP_TRY(hipSetDevice(ix->device));
         PageSplit sp{};
-        if (m) sp = PageSplit{j.nb, p->ids, p->dist, p->count, m->h_need_dense, m->h_need_dense + m->flags_cap};
+        if (m) sp = PageSplit{j.nb, p->ids, p->dist, p->count, m->h_need_dense, m->h_need_dense + m->flags_cap, c.done};
         PVS_TRY(enqueue_joined_pass(ix, c, nb, j.k, j.metric, j.ids, j.dist, j.count, m ? &sp : nullptr));
-        if (m) HIP_TRY(hipEventRecord(m->done, c.side_finalize ? ix->fin_stream : c.stream));
+        if (m) {
+            HIP_TRY(hipEventRecord(m->done, c.side_finalize ? ix->fin_stream : c.stream));
+            if (c.side_finalize) {  // (the partner's part of pass C reads c's buffers after c's own ticket has completed)
+                HIP_TRY(hipEventRecord(c.tail, ix->fin_stream));
+                c.tail_pending = true;
+            }
+        }
         return PVS_OK;
     };
     const pvs_status st = body();
